@@ -12,9 +12,22 @@ leaves during its end-of-launch drain, as consecutive batches of a running node 
 Launch: `python bench.py --gpus N` starts its own N rank processes (children, one per GPU) when it is not
 already under torch.distributed.run; under torch.distributed.run each process is one rank.
 
-Output: one JSON line on rank 0 with the contract fields plus `roofline` (VALU-bound), the end-to-end
-host-buffer rates (`e2e_verifies_per_s`) and `cpu_baseline` (the oracle on every usable host core, bounded
-sample).
+Output: one JSON line on rank 0 with the contract fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`) plus the algorithmic `roofline` (VALU-bound) of the timed steps.
+
+A plain run does only what that figure needs: set up, warm up, time `--steps` steps, check the verdict bitmaps, write
+them if `--dump-outputs DIR` is given, print the line. `--full` adds every other leg, each in runs of its own after
+the timed steps: one launch alone (`launch_ms_alone`), the per-rank diagnostics at N > 1 (`multi_gpu`), the end-to-end
+host-buffer rates (`e2e_verifies_per_s`, `e2e_abi*`), AT2 traffic and sender churn through comb contexts
+(`at2_traffic`, `sender_churn`), the CPU baselines (`cpu_baseline`: the oracle, OpenSSL and the product's CPU backend
+on every usable host core, bounded samples) and the rocprofv3 counter passes (`roofline.traffic`,
+`roofline.valu_measured`). The per-leg options (`--e2e`, `--traffic-leg`, `--churn-legs`, `--cpu-sample`,
+`--pmc-traffic`) choose among those legs under `--full` and do nothing without it.
+
+`--dump-outputs DIR` writes what the last timed step computed, the verdicts a caller of the verify call reads from
+its bitmap, as `DIR/verdicts.npy` (float32, 1.0 = valid, one per record in record order; at N > 1 the gathered node
+bitmap, all ranks' records). The records come from the seeded GPU generator, so the same arguments give the same
+inputs and two builds can be compared verdict for verdict.
 """
 import argparse
 import json
@@ -86,7 +99,16 @@ def parse():
     ap.add_argument("--pmc-traffic", type=int, default=1,
                     help="1 = at N=1, measure HBM-side bytes per verify launch with two rocprofv3 PMC passes "
                          "(FETCH_SIZE, WRITE_SIZE) of a 2-step child run; 0 = skip (roofline.traffic null)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (launch alone, multi-GPU diagnostics, host-buffer "
+                         "paths, AT2 traffic, sender churn, CPU baselines, PMC passes); without it the per-leg options "
+                         "above do nothing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the verdicts of the last timed step to DIR/verdicts.npy (float32, one per record)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _free_port():
@@ -277,31 +299,40 @@ def main():
     elapsed = time.perf_counter() - t0
     # device time per step on the launch streams: the verify kernels (N = 1) or kernels + all-gathers (N > 1)
     kernel_ms = max(ev0.elapsed_time(e) for e in kend) / args.steps
-    # one launch alone (nothing before or after it on the device): its duration is what a kernel-trace profile of a
-    # single launch reports; the timed steps overlap by up to the end-of-launch drain
-    ea, eb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ea.record(lstreams[0])
-    verify(*ptrs, 0)
-    eb.record(lstreams[0])
-    barrier()
-    launch_ms_alone = ea.elapsed_time(eb)
-    kernel_ms_local, elapsed_local, launch_alone_local = kernel_ms, elapsed, launch_ms_alone
     progress(f"timed steps done: {kernel_ms:.3f} ms per step on the device")
-    elapsed, kernel_ms, launch_ms_alone = reduce([elapsed, kernel_ms, launch_ms_alone],
-                                                 dist.ReduceOp.MAX if use_dist else None)
 
     # verdict check after the timed region: every generated record must be valid, on every rank (N > 1: the
     # gathered node bitmaps, all ranks' records), in the bitmap of every launch stream the steps used
     used = d_alls if use_dist else d_vers
     used = used[: min(2, max(1, args.steps + args.warmup))]
-    match = min(float((full == -1).float().mean().item()) for full in used)
+    match = min(float((bitmap == -1).float().mean().item()) for bitmap in used)
     match = reduce([match], dist.ReduceOp.MIN)[0] if use_dist else match
 
+    if args.dump_outputs and rank == 0:  # the bitmap the last timed step wrote, before any other leg launches
+        last = (d_alls if use_dist else d_vers)[(args.steps - 1) % 2]
+        dump_outputs(args.dump_outputs, at2v, np, last.cpu().numpy().view(np.uint32), n * world)
+        progress(f"outputs written to {args.dump_outputs}")
+
+    launch_ms_alone = None
+    if args.full:
+        # one launch alone (nothing before or after it on the device): its duration is what a kernel-trace profile of
+        # a single launch reports; the timed steps overlap by up to the end-of-launch drain
+        ea, eb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ea.record(lstreams[0])
+        verify(*ptrs, 0)
+        eb.record(lstreams[0])
+        barrier()
+        launch_ms_alone = ea.elapsed_time(eb)
+    kernel_ms_local, elapsed_local, launch_alone_local = kernel_ms, elapsed, launch_ms_alone
+    elapsed, kernel_ms = reduce([elapsed, kernel_ms], dist.ReduceOp.MAX if use_dist else None)
+    if args.full:
+        launch_ms_alone = reduce([launch_ms_alone], dist.ReduceOp.MAX if use_dist else None)[0]
+
     multi = multi_gpu_diagnostics(args, v, barrier, dist, torch, lstreams, ptrs, n, L, words, d_vers, d_alls, world,
-                                  kernel_ms_local, elapsed_local, launch_alone_local) if use_dist else None
+                                  kernel_ms_local, elapsed_local, launch_alone_local) if use_dist and args.full else None
 
     e2e = host_path(args, v, verify, barrier, reduce, dist, torch, dev, lstreams, d_pk, d_sig, d_msg, d_off, d_vers,
-                    d_alls, n, L, words, use_dist, world) if args.e2e else None
+                    d_alls, n, L, words, use_dist, world) if args.e2e and args.full else None
 
     total = n * world * args.steps
     value = total / elapsed
@@ -379,18 +410,19 @@ def main():
             out["multi_gpu"] = multi
     if e2e:
         progress("host-buffer leg done")
-    if rank == 0 and world == 1 and args.e2e and not use_dist:
+    if args.full and rank == 0 and world == 1 and args.e2e and not use_dist:
         out.update(abi_host_leg(args, v, d_pk, d_sig, d_msg, d_off, n, L, value))
         progress("library host-buffer call leg done")
-    if rank == 0 and world == 1 and args.traffic_leg and not args.senders and not use_dist:
+    if args.full and rank == 0 and world == 1 and args.traffic_leg and not args.senders and not use_dist:
         progress("AT2-traffic leg")
         out["at2_traffic"] = at2_traffic_leg(args, at2v, torch, dev, lstreams, n, L)
-    if rank == 0 and world == 1 and args.churn_legs not in ("", "0") and not args.senders and not use_dist:
+    if (args.full and rank == 0 and world == 1 and args.churn_legs not in ("", "0") and not args.senders
+            and not use_dist):
         out["sender_churn"] = churn_legs(args, at2v, torch, dev, lstreams, n, L, kernel_ms, value)
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         progress("CPU baseline")
         out["cpu_baseline"] = cpu_baseline(args, d_pk, d_sig, d_msg, n, L)
-    if rank == 0 and world == 1 and args.pmc_traffic and not use_dist:
+    if args.full and rank == 0 and world == 1 and args.pmc_traffic and not use_dist:
         progress("PMC passes")
         tr = pmc_traffic(args, n, L)
         if tr is not None:
@@ -412,6 +444,20 @@ def main():
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_MAX_RECORDS = 1 << 22  # 16 MiB of float32 verdicts; beyond that a fixed, seeded sample of this many records
+
+
+def dump_outputs(path, at2v, np, words, total):
+    """--dump-outputs: the verdict bitmap of the last timed step as DIR/verdicts.npy, float32, 1.0 = valid, one per
+    record in record order. More than DUMP_MAX_RECORDS records: the verdicts at a sorted sample of that many record
+    indices drawn without replacement by a generator seeded with CFG_SEED (the same indices in every run)."""
+    ver = at2v.unpack_verdicts(words, total).astype(np.float32)
+    if total > DUMP_MAX_RECORDS:
+        ver = ver[np.sort(np.random.default_rng(CFG_SEED).choice(total, DUMP_MAX_RECORDS, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "verdicts.npy"), ver)
 
 
 def at2_traffic_leg(args, at2v, torch, dev, lstreams, n, L, senders=64):

@@ -13,7 +13,7 @@ for r in $(seq 1 $ROUNDS); do
   for v in $A $B; do
     cp at2-node_amd/at2v/variants/libat2v_$v.so $L
     echo "[ab_churn] round $r variant $v"
-    timeout -k 10 240 python3 bench.py --steps 10 --cpu-sample 0 --pmc-traffic 0 --e2e 0 > $D/churn_${v}_$r.txt 2>&1 \
+    timeout -k 10 240 python3 bench.py --full --steps 10 --cpu-sample 0 --pmc-traffic 0 --e2e 0 > $D/churn_${v}_$r.txt 2>&1 \
       || { echo "[ab_churn] $v FAILED rc=$?"; tail -20 $D/churn_${v}_$r.txt; cp $D/.orig.so $L; exit 1; }
     grep "^{" $D/churn_${v}_$r.txt | python3 -c "
 import json, sys

@@ -9,9 +9,9 @@
 #   probe=<expr>  pytest -m gpu -k <expr>, output gpu_probe<N>.txt; test failures (exit 1) do not end the run, any other
 #                 failure (time limit, crash) does
 #   smoke         __graft_entry__.smoke()
-#   bench         python bench.py (the default driver line: config 2 + at2_traffic + roofline + cpu_baseline)
-#   benchat2      python bench.py on AT2 traffic as the main leg (64 senders, combs) with the PMC passes
-#   bench1        python bench.py with the PMC passes and CPU baseline off (a quick rate check)
+#   bench         python bench.py --full (the whole driver line: config 2 + at2_traffic + roofline + cpu_baseline)
+#   benchat2      python bench.py --full on AT2 traffic as the main leg (64 senders, combs) with the PMC passes
+#   bench1        python bench.py --full with the PMC passes and CPU baseline off (a quick rate check)
 #   torchrun1     the world-1 torchrun rehearsal of the N > 1 bench path (RCCL gather inside the timed loop)
 #   torchrun3     the same with config 3's per-rank load (2M records per rank: 16M over 8 GPUs)
 #   rocprof       rocprofv3 --kernel-trace --stats of a bench run with one scratch set (per-kernel averages)
@@ -65,21 +65,21 @@ for st in "$@"; do
              mkdir -p $D/probe$NPROBE && cp gpurun_out/config5_*.json $D/probe$NPROBE/ 2>/dev/null
              [ $rc -le 1 ] || { echo "[gpu_run] probe$NPROBE FAILED rc=$rc"; exit 1; } ;;
     smoke) run smoke 180 python3 -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 500 python3 bench.py
+    bench) run bench 500 python3 bench.py --full
            grep '^{' $D/bench.txt > $D/bench.json ;;
-    benchat2) run benchat2 400 python3 bench.py --senders 64 --sender-cache 1024 --sender-comb 1 --cpu-sample 0 --e2e 0
+    benchat2) run benchat2 400 python3 bench.py --full --senders 64 --sender-cache 1024 --sender-comb 1 --cpu-sample 0 --e2e 0
               grep '^{' $D/benchat2.txt > $D/benchat2.json ;;
-    bench1) run bench1 300 python3 bench.py --pmc-traffic 0 --cpu-sample 0 --e2e 0
+    bench1) run bench1 300 python3 bench.py --full --pmc-traffic 0 --cpu-sample 0 --e2e 0
             grep '^{' $D/bench1.txt > $D/bench1.json ;;
     torchrun1) run torchrun1 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-                 --master-port 29533 bench.py --gpus 1 --steps 10 --warmup 2 --e2e 0
+                 --master-port 29533 bench.py --gpus 1 --full --steps 10 --warmup 2 --e2e 0
                grep '^{' $D/torchrun1.txt > $D/torchrun1.json ;;
     torchrun3) run torchrun3 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-                 --master-port 29534 bench.py --gpus 1 --steps 10 --warmup 2 --e2e 0 --records-per-gpu 2097152
+                 --master-port 29534 bench.py --gpus 1 --full --steps 10 --warmup 2 --e2e 0 --records-per-gpu 2097152
                grep '^{' $D/torchrun3.txt > $D/torchrun3.json ;;
     rocprof) export AT2V_SCRATCH_SETS=1
              run rocprof 400 rocprofv3 --kernel-trace --stats --output-format csv -d $D/prof -o run -- \
-               python3 bench.py --steps 20 --warmup 3 --pmc-traffic 0 --cpu-sample 0 --e2e 0 --churn-legs 0
+               python3 bench.py --full --steps 20 --warmup 3 --pmc-traffic 0 --cpu-sample 0 --e2e 0 --churn-legs 0
              unset AT2V_SCRATCH_SETS
              find $D/prof -name '*kernel_stats.csv' -exec cp {} $D/kernel_stats.csv \; ;;
     latab) for r in 1 2; do for v in 0 1; do
