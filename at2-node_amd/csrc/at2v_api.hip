@@ -35,28 +35,8 @@
 #include "at2v_cache.h"
 #include "at2v_cpu.h"
 #include "at2v_env.h"
+#include "at2v_launch.h"
 #include "at2v_shard.h"
-
-namespace at2v {
-hipError_t launch_verify(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, uint32_t msg_total,
-                         const uint32_t* off, uint32_t n, int policy, uint32_t* verdicts, int4* scratch,
-                         const int4* btab, const int4* btab24, int grid, uint32_t pair_max, hipStream_t stream,
-                         const CacheArgs* cache, const PartArgs* part, int dense, const StagedArgs* staged);
-size_t btab_bytes();
-size_t ladder_btab_bytes();
-hipError_t launch_build_ladder_btab(int4* out, void* scratch, hipStream_t stream);
-hipError_t launch_build_btab(int4* out, hipStream_t stream);
-hipError_t launch_gen(uint64_t cfg, uint64_t first, uint32_t n, uint32_t msg_len, uint64_t senders,
-                      const uint64_t* keys, uint8_t* pk, uint8_t* sig, uint8_t* msg, uint32_t* off, hipStream_t stream);
-hipError_t launch_sign(const uint8_t* seeds, const uint8_t* msg, uint32_t msg_total, const uint32_t* off, uint32_t n,
-                       uint8_t* pk, uint8_t* sig, hipStream_t stream);
-hipError_t launch_decode(const uint8_t* pts, uint32_t n, uint32_t* out, hipStream_t stream);
-hipError_t verify_occupancy(int* blocks_per_cu, int* vgprs);
-size_t scratch_bytes_per_block();
-size_t scratch_bytes(int grid);
-int block_threads();
-unsigned kernel_experiments();
-}  // namespace at2v
 
 namespace {
 
@@ -214,7 +194,6 @@ struct Shard {
   DevBuf scratch[4];
   DevBuf part[4];  // per scratch set: the classify kernel's hit / miss lists (partitioned cached launches)
   DevBuf btab, pk, sig, msg, off, verdict;
-  const int4* btab24 = nullptr;  // the throughput ladder's 24-bit fixed-base tables, shared per device (bcomb_acquire)
   hipEvent_t copied = nullptr;  // the verdict copy of a device-side call (decode, sharded)
   DevBuf hverdict[3];            // host-buffer calls: the shard's device bitmap per call slot (HostCall)
   hipEvent_t hcopied[3] = {nullptr, nullptr, nullptr};  // ... and its verdict copy (the call waits for this, not for
@@ -296,10 +275,6 @@ int hip_code(hipError_t e) {
     if (e_ != hipSuccess) return hip_code(e_); \
   } while (0)
 
-constexpr int kLadderKey = -24;  // bcomb_acquire's key for the ladder tables (the combs use their window width)
-hipError_t bcomb_acquire(int device, int bits, hipStream_t st, const int4** out);
-void bcomb_release(const int4* p);
-
 int init_shard(Shard& s, int device) {
   s.device = device;
   AT2V_TRY(hipSetDevice(device));
@@ -319,12 +294,10 @@ int init_shard(Shard& s, int device) {
     AT2V_TRY(hipEventRecord(s.scratch_free[j], s.stream));
     AT2V_TRY(s.scratch[j].ensure(at2v::scratch_bytes(s.grid)));
   }
-  // fixed-base table [0..2^(AT2V_BWIN-1)]B, built on the device once per context
+  // fixed-base tables [0..2^15]B and [0..2^15] 2^128 B, built on the device once per context
   AT2V_TRY(s.btab.ensure(at2v::btab_bytes()));
   AT2V_TRY(at2v::launch_build_btab((int4*)s.btab.p, s.stream));
   AT2V_TRY(hipStreamSynchronize(s.stream));
-  // the throughput kernels' 24-bit tables [j]B, [j 2^144]B (2 GB, kernels' AT2V_LADDER_BW), one copy per device
-  if (at2v::ladder_btab_bytes()) AT2V_TRY(bcomb_acquire(device, kLadderKey, s.stream, &s.btab24));
   return AT2V_OK;
 }
 
@@ -333,7 +306,7 @@ bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) &
 // The combs of B, shared by every comb context of the process on a device (round 6, VERDICT r5 "Next" 3): built by the
 // first context that needs one (on its stream, synchronously, under the registry's lock: a few ms since they are built by
 // additions), freed with the last. A node's ingest queue and its batch contexts hold one 872 MB + 67 MB pair per device
-// instead of one each. The ladder's 24-bit tables (key kLadderKey, every GPU context) are shared the same way.
+// instead of one each.
 struct SharedBComb {
   int device, bits;
   int4* p;
@@ -355,16 +328,14 @@ hipError_t bcomb_acquire(int device, int bits, hipStream_t st, const int4** out)
     }
   int4* p = nullptr;
   void* scratch = nullptr;
-  const bool ladder = bits == kLadderKey;
-  hipError_t e = hipMalloc((void**)&p, ladder ? at2v::ladder_btab_bytes() : at2v::bcomb_bytes(bits));
+  hipError_t e = hipMalloc((void**)&p, at2v::bcomb_bytes(bits));
   if (e == hipSuccess) e = hipMalloc(&scratch, at2v::bcomb_scratch_bytes());
 #if AT2V_EXP_BCOMB_NOBUILD  // EXPERIMENT (wrong verdicts on the hit path): the hit-list table allocated but never written
-  const bool build = ladder || bits == at2v::bcomb_lat_bits();
+  const bool build = bits == at2v::bcomb_lat_bits();
 #else
   const bool build = true;
 #endif
-  if (e == hipSuccess && build)
-    e = ladder ? at2v::launch_build_ladder_btab(p, scratch, st) : at2v::launch_build_bcomb(p, bits, scratch, st);
+  if (e == hipSuccess && build) e = at2v::launch_build_bcomb(p, bits, scratch, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (scratch) (void)hipFree(scratch);
   if (e != hipSuccess) {
@@ -611,7 +582,7 @@ hipError_t launch_shard(at2v_ctx* ctx, Shard& s, const uint8_t* pk, const uint8_
   }
   if (e == hipSuccess)
     e = at2v::launch_verify(pk, sig, msg, msg_bytes, off, n, (int)ctx->policy, verdicts, (int4*)s.scratch[j].p,
-                            (const int4*)s.btab.p, s.btab24, s.grid, pair_max, stream, c ? &ca : nullptr,
+                            (const int4*)s.btab.p, s.grid, pair_max, stream, c ? &ca : nullptr,
                             part ? &pa : nullptr, pipeline ? 1 : 0, staged);
   if (e == hipSuccess && c) {
     // claims of this launch -> payloads on the build stream (later launches use them; this one did not wait)
@@ -1108,9 +1079,9 @@ at2v::CpuPool* copy_pool(at2v_ctx* ctx) {
 
 int nccl_code(ncclResult_t r) { return r == ncclSuccess ? AT2V_OK : AT2V_E_RCCL; }
 
-// AT2V_EXPERIMENT_* bits of this library: the kernels object's switches and this file's
+// AT2V_EXPERIMENT_* bits of this library (the kernels object has no experiment builds any more)
 unsigned library_experiments() {
-  unsigned m = at2v::kernel_experiments();
+  unsigned m = 0;
 #if AT2V_EXP_BCOMB_NOBUILD
   m |= AT2V_EXPERIMENT_BCOMB_NOBUILD;
 #endif
@@ -1279,7 +1250,6 @@ void at2v_destroy(at2v_ctx* ctx) {
     for (DevBuf& b : s.scratch) b.release();
     for (DevBuf& b : s.part) b.release();
     s.btab.release();
-    bcomb_release(s.btab24);
     s.pk.release();
     s.sig.release();
     s.msg.release();

@@ -1,5 +1,5 @@
-// at2v_cache.h — device buffers of the per-sender A cache (at2v_opts.sender_cache), shared by the launcher
-// (at2v_kernels.hip) and the context (at2v_api.hip). AT2 senders issue consecutive sequences
+// at2v_cache.h — device buffers of the per-sender A cache (at2v_opts.sender_cache), shared by the kernels
+// (at2v_kernels.hip) and the context (at2v_api.hip); the launchers that take them are declared in at2v_launch.h. AT2 senders issue consecutive sequences
 // (/root/reference/src/bin/server/accounts/account.rs:36-43), so one key signs many payloads of a node batch; the cache
 // keeps, per distinct A, dalek's decode verdict and a payload derived from A alone: the table [j]A the ladder kernel
 // would otherwise rebuild per record, or (sender_comb) the comb of -A that replaces the doublings.
@@ -40,7 +40,7 @@ struct CacheArgs {
   const int4* bcomb;         // sender_comb: the hit-list kernel's comb of B: kBCombMidBits-bit windows (872 MB), or
                              // with AT2V_CTX_BCOMB_WIDE kBCombBits-bit ones (11.8 GB)
   int bcomb_bits;            // bcomb's window (20 or 24)
-  unsigned long long* ctl;   // counters, kCtl* in at2v_kernels.hip
+  unsigned long long* ctl;   // counters, CacheCtlWord below
   uint64_t seed;             // fingerprint key (random per context)
   uint64_t fp_mask;          // fingerprint bits kept (all in the product; fewer in a test that forces collisions)
   // Admission (round 5): a key not in the table claims a tag and a payload only if it was sighted before (its
@@ -67,7 +67,6 @@ struct PartArgs {
   uint32_t* midx;    // record indices of the misses (counts[1])
   uint32_t* counts;  // [0] hits, [1] misses (zeroed before the classify kernel)
 };
-size_t part_bytes_per_record();
 
 // A host-buffer batch verified by ONE launch while its records are still being uploaded (at2v_api.hip, the staged
 // form of the host pipeline). The shard's records are in nreg regions of 2^ushift records (the last one: last_c), each
@@ -94,17 +93,6 @@ struct CacheCompactArgs {
   uint32_t* used;  // capacity flags: payload kept
 };
 
-size_t cache_entry_bytes();
-size_t cache_payload_bytes(int comb);  // one key's payload: table [j]A or comb
-size_t bcomb_bytes(int bits);          // a comb of B with bits-bit windows (16, 20 or 24)
-int bcomb_lat_bits();
-int bcomb_mid_bits();
-int bcomb_wide_bits();
-// build a comb of B into out (bcomb_bytes(bits)), asynchronously on stream; scratch: bcomb_scratch_bytes() of device
-// memory the launches use until they complete
-size_t bcomb_scratch_bytes();
-hipError_t launch_build_bcomb(int4* out, int bits, void* scratch, hipStream_t stream);
-int cache_ctl_words();
 // ctl word indices the host reads (at2v_get_info) and resets
 enum CacheCtlWord : int {
   kCtlFreeHead = 0,  // payload indices handed out since the last compaction
@@ -131,12 +119,5 @@ enum CacheCtlWord : int {
   kCtlHist,          // 64 age buckets
   kCtlWordsTotal = kCtlHist + 64
 };
-// initialise a fresh cache: free list 0..capacity-1 (stream order)
-hipError_t launch_cache_init(const CacheArgs& c, hipStream_t stream);
-// build stream, after the launch that filled claim slot c (c.new_list, count word c.count_word): build the payloads it
-// claimed, mark them valid, reset the slot's count
-hipError_t launch_cache_build(const CacheArgs& c, uint32_t max_claims, hipStream_t stream);
-// compact a full cache into (x.new_tags, x.new_entries) (stream order; no cached launch or build may be in flight)
-hipError_t launch_cache_compact(const CacheArgs& c, const CacheCompactArgs& x, hipStream_t stream);
 
 }  // namespace at2v

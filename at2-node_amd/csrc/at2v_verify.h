@@ -249,6 +249,9 @@ AT2V_HD AT2V_INLINE int verify_core(const uint32_t Rw[8], const uint32_t Aw[8], 
 //   Pace : mark(units) after each phase, window() at each ladder window start, mid() after its doublings
 //          (progress, ~1 unit per window; NoPace = none)
 struct NoPace {
+#ifdef AT2V_WAIT_PROBE
+  unsigned long long probe[4] = {0, 0, 0, 0};  // the probe build's sums land here for an unpaced caller (never read)
+#endif
   AT2V_HD AT2V_INLINE void mark(uint32_t) {}
   AT2V_HD AT2V_INLINE void window() {}
   AT2V_HD AT2V_INLINE void mid() {}

@@ -102,7 +102,9 @@ enum {
 
 /* Timing-only experiment switches a library may have been compiled with (AT2V_EXP_* build macros; each makes some
  * verdicts WRONG). at2v_create fails with AT2V_E_INVALID on such a build unless the environment variable
- * AT2V_ALLOW_EXPERIMENT is "1", and at2v_info.experiments reports the bits. A shipped build has none. */
+ * AT2V_ALLOW_EXPERIMENT is "1", and at2v_info.experiments reports the bits. A shipped build has none. Only
+ * BCOMB_NOBUILD can still be built; the kernel-side builds (TAB128, COMB_HOT, SLOT_WAVES, CONST_MSG, COMB3) are retired
+ * and their bits stay reserved. */
 #define AT2V_EXPERIMENT_TAB128 1u        /* 128-byte [j]A table entries, the last 8 words dropped */
 #define AT2V_EXPERIMENT_COMB_HOT 2u      /* every A-comb entry read is the same cache line */
 #define AT2V_EXPERIMENT_SLOT_WAVES 4u    /* waves share per-lane table slots */

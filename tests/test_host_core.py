@@ -61,8 +61,8 @@ def test_sanitized_host_build_of_device_core(host_exe_asan, half):
 @pytest.mark.parametrize("half", MODES, ids=MODE_IDS)
 @pytest.mark.parametrize("name", golden_io.SETS)
 def test_host_build_of_device_core_matches_golden(host_exe, name, half):
-    """every verify form the kernels can be built with: the full-length ladder (verify_core), the half-size lattice
-    form on the signed field (verify_half) and on the unsigned chained-carry field (verify_half_fu, the throughput
+    """every verify form of the shared headers: the full-length ladder (verify_core, round 1's kernel), the half-size
+    lattice form on the signed field (verify_half) and on the unsigned chained-carry field (verify_half_fu, the throughput
     kernel), its two-lanes-per-record split (verify_pair_part + verify_pair_combine, the low-latency kernel), and the
     sender-comb form (comb_build_lane + verify_comb_fu, at2v_comb.h) and its low-latency four-wave split (comb_decode_r,
     comb_sum over the halves, comb_check_split) on the first 1,200 records of a set (every distinct key builds its

@@ -1,8 +1,7 @@
 // Phase breakdown of the verify kernel on gfx950: the product kernel (at2v_kernels.hip, included
 // verbatim) built with AT2V_PHASE(k) = "lane 0 adds the s_memtime delta since the previous mark to
-// bucket k of its wave". Buckets (full-length path): 0 loop/pair overhead, 1 loads + V1 + decompress A,
-// 2 SHA-512 + mod l + recode, 3 A table, 4 ladder, 5 group inversion, 6 encode + compare + verdict store;
-// (half-size path): 1 adds decoding R, 2 adds the lattice reduction, 3 builds both tables, 6 = identity check.
+// bucket k of its wave". Buckets: 0 loop overhead, 1 loads + V1 + decoding A and R, 2 t = c1 s mod l + recode,
+// 3 both tables, 4 ladder, 5 SHA-512 + mod l, 6 identity check + verdict store, 7 lattice reduction.
 // Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -I at2-node_amd/csrc tools/phase_bench.hip -o tools/phase_bench
 #include <hip/hip_runtime.h>
 
@@ -88,7 +87,7 @@ int main(int argc, char** argv) {
   CHECK(hipMalloc(&scratch, at2v::scratch_bytes(grid)));
   CHECK(hipMalloc(&btab, at2v::btab_bytes()));
   CHECK(at2v::launch_build_btab(btab, 0));
-  CHECK(at2v::launch_gen(0x4154325F, 0, n, L, pk, sig, msg, off, 0));
+  CHECK(at2v::launch_gen(0x4154325F, 0, n, L, 0, nullptr, pk, sig, msg, off, 0));
   CHECK(hipDeviceSynchronize());
   std::vector<unsigned long long> zero(AT2V_MAX_WAVES * 8, 0), zl(AT2V_MAX_WAVES, 0);
   float ms = 0;
@@ -104,7 +103,8 @@ int main(int argc, char** argv) {
     CHECK(hipEventCreate(&e0));
     CHECK(hipEventCreate(&e1));
     CHECK(hipEventRecord(e0, 0));
-    CHECK(at2v::launch_verify(pk, sig, msg, n * L, off, n, 0, ver, scratch, btab, grid, pair_max, 0));
+    CHECK(at2v::launch_verify(pk, sig, msg, n * L, off, n, 0, ver, scratch, btab, grid, pair_max, 0, nullptr, nullptr, 0,
+                              nullptr));
     CHECK(hipEventRecord(e1, 0));
     CHECK(hipEventSynchronize(e1));
     CHECK(hipEventElapsedTime(&ms, e0, e1));
@@ -115,13 +115,8 @@ int main(int argc, char** argv) {
   CHECK(hipMemcpy(hv.data(), ver, hv.size() * 4, hipMemcpyDeviceToHost));
   size_t valid = 0;
   for (uint32_t i = 0; i < n; ++i) valid += (hv[i / 32] >> (i % 32)) & 1;
-#if AT2V_VERIFY_HALF
   const char* names[8] = {"loop overhead", "loads+V1+decode A,R", "t = c1 s mod l + recode", "A,R tables",
                           "ladder", "sha512 + mod l", "identity check+store", "lattice reduction"};
-#else
-  const char* names[8] = {"pair/loop overhead", "loads+V1+decompress", "sha512+mod l+recode", "A table",
-                          "ladder", "group inversion", "encode+compare+store", "-"};
-#endif
   double tot = 0, b[8] = {0};
   const int waves = grid * wpb;
   for (int w = 0; w < waves; ++w)
