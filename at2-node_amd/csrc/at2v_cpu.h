@@ -35,4 +35,9 @@ void cpu_verify_batch(CpuPool* p, const uint8_t* pk, const uint8_t* sig, const u
 // bit i of valid_words = 1 iff pts[i] decodes under dalek rules (the kernels' gu_frombytes), synchronous
 void cpu_decode_points(CpuPool* p, const uint8_t* pts, size_t n, uint32_t* valid_words);
 
+// One record through the joint-table form of the verify routine (verify_half_fu_joint, what the GPU's verify_kernel
+// runs) with the host tables: the verdict at2v_verify_one_policy gives, 0 or 1. For tests (tests/host/joint_host.cpp);
+// not part of the ABI. Arguments as at2v_verify_one_policy's, already checked.
+int cpu_verify_one_joint(const uint8_t pk[32], const uint8_t sig[64], const uint8_t* msg, uint32_t len, int policy);
+
 }  // namespace at2v

@@ -153,6 +153,49 @@ struct DevTabA {
   }
 };
 
+// The joint table of verify_half_fu_joint: entries 1..11 (packed as DevTabA's, stored by DevTabA::store) in the first
+// 88 granules of the lane slot, read through the wave's two LDS stages as a double buffer (window i's entry through
+// stage i & 1; the stage index is wave-uniform).
+constexpr int kJointGranules = (kJointEntries - kIdentShared) * 8;
+static_assert(kJointGranules <= kLaneGranules, "the joint table fits the lane slot");
+struct DevTabJ {
+  DevTabA t;   // base: the lane slot; stage: stage 0
+  int stage1;  // stage 1, in granules from stage 0 (one base pointer: both stay provably LDS addresses)
+  __device__ AT2V_INLINE int4* stage_of(int st) const { return t.stage + (st ? stage1 : 0); }
+  template <class Cached>
+  __device__ AT2V_INLINE void store(int e, const Cached& c) const {
+    t.store(e, c);
+  }
+  // stage_just_read: the stage's previous entry was read with no arithmetic on it since (wait for those LDS reads)
+  __device__ AT2V_INLINE void prefetch(int st, int e, bool stage_just_read) const {
+    if (stage_just_read) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const int4* src = (kIdentShared && e == 0) ? t.ident : t.base + (e - kIdentShared) * 8;
+    int4* const stg = stage_of(st);
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+      __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(src + q),
+                                       (__attribute__((address_space(3))) void*)(stg + q * 64), 16, 0, 0);
+  }
+  template <class Cached>
+  __device__ AT2V_INLINE void load_prefetched(int st, Cached& c) const {
+    static_assert(sizeof(Cached) == 160, "cached point: 40 words");
+    AT2V_PROBE(t.waited, asm volatile("s_waitcnt vmcnt(0)" ::: "memory"));
+    int4* const stg = stage_of(st);
+    uint32_t pw[32];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int4 v = stg[q * 64 + t.lane];
+      pw[4 * q] = (uint32_t)v.x;
+      pw[4 * q + 1] = (uint32_t)v.y;
+      pw[4 * q + 2] = (uint32_t)v.z;
+      pw[4 * q + 3] = (uint32_t)v.w;
+    }
+    fu* cf = reinterpret_cast<fu*>(&c);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) fu_unpack8(cf[k], pw + 8 * k);
+  }
+};
+
 struct LdsTabB {
   const int4* lds;  // AT2V_BTAB_ENTRIES x 8 granules
   __device__ AT2V_INLINE void load(int e, ge_niels& n) const {

@@ -6,7 +6,9 @@
 //   * persistent grid of 512-thread blocks (both waves of every SIMD in one workgroup, paced against each other); a
 //     wave's first chunk is its index, later ones come from a per-launch queue counter; each wave reuses a fixed
 //     160 KiB slice of the scratch buffer for its 64 lanes' tables [1..8]A and [1..8](+-R) (cached form packed into
-//     128 B per entry, lane-contiguous; entry 0, the identity, is one shared entry after the B tables);
+//     128 B per entry, lane-contiguous; entry 0, the identity, is one shared entry after the B tables); verify_kernel,
+//     which takes nothing from a sender cache, keeps ONE joint table of A and R there instead (11 entries, 2-bit
+//     windows: verify_half_fu_joint, DESIGN.md §4b "Joint table");
 //   * the fixed-base tables [0..2^15]B and [0..2^15] 2^128 B (affine Niels, 128 B per entry, 8.4 MB) are
 //     built once per context and stay L2/MALL-resident; table entries reach the lanes by LDS-DMA;
 //   * records are read straight from the ABI layout (pk n x 32, sig n x 64, msg + offsets) with
@@ -240,6 +242,10 @@ __device__ AT2V_INLINE void verify_chunks(
       good = verify_half_fu<true>(Rw, Aw, Sw, len, msgword, policy, tc, tr, tb0, tb1, wmax, pace, all_hit, a_ok) & act;
     } else if (skip) {
       good = 0;
+    } else if constexpr (!kCache && !kPart && !kStaged) {
+      // verify_kernel: nothing comes from a sender cache, so A and R share one joint table (the slot's first 88 granules)
+      DevTabJ tj{ta, (int)(tr.stage - ta.stage)};
+      good = verify_half_fu_joint(Rw, Aw, Sw, len, msgword, policy, tj, tb0, tb1, wmax, pace) & act;
     } else {
       good = verify_half_fu<false>(Rw, Aw, Sw, len, msgword, policy, ta, tr, tb0, tb1, wmax, pace) & act;
     }

@@ -127,6 +127,32 @@ AT2V_HD AT2V_INLINE void sc_recode4_hi8(uint32_t out[8], const uint32_t s[8]) {
   }
 }
 
+// Signed radix-4 digits d_i in {-1, 0, 1, 2} of a value < 2^255 (the joint ladder of verify_half_fu_joint), stored as
+// d_i + 1 in 2 bits, 16 per word: word j holds digits 16j..16j+15 (digit 16j+m at bits 2m, 2m+1). A raw digit plus its
+// carry-in of 3 or 4 becomes -1 or 0 with a carry out, so the stored string is simply s + 0x55..55: adding 1 to every
+// raw digit makes exactly those cases carry and leaves d_i + 1 behind. Returns the digit count, the smallest m with
+// s <= 2 (4^m - 1) / 3 (1 + the index of the top non-zero digit: that digit is positive; 0 for s = 0), or 129 when
+// the 128 digits cannot hold s (only for s >= 2^255: the sum carries out of the top word).
+AT2V_HD AT2V_INLINE int sc_recode2(uint32_t out[8], const uint32_t s[8]) {
+  uint64_t c = 0;
+  int nd = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    c += (uint64_t)s[j] + 0x55555555u;
+    out[j] = (uint32_t)c;
+    c >>= 32;
+    const uint32_t x = out[j] ^ 0x55555555u;  // non-zero digits
+    if (x) nd = 16 * j + (33 - __builtin_clz(x)) / 2;
+  }
+  return c ? 129 : nd;
+}
+
+// Both scalars of the joint ladder: digits of c0 and |c1|, and the larger of the two digit counts.
+AT2V_HD AT2V_INLINE int sc_recode2_joint(uint32_t d0[8], uint32_t d1[8], const uint32_t c0[8], const uint32_t c1[8]) {
+  const int n0 = sc_recode2(d0, c0), n1 = sc_recode2(d1, c1);
+  return n0 > n1 ? n0 : n1;
+}
+
 // Signed radix-256 digits e_0..e_31 of a scalar < 2^253, e_i in [-128, 127], stored as (e_i + 128)
 // bytes: word j holds digits 4j..4j+3.
 AT2V_HD AT2V_INLINE void sc_recode8(uint32_t out[8], const uint32_t s[8]) {

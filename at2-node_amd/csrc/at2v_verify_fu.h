@@ -410,6 +410,262 @@ AT2V_HD AT2V_INLINE int verify_half_fu(const uint32_t Rw[8], const uint32_t Aw[8
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// The joint form (DESIGN.md §4b "Joint table"): [c0]A + [c1]R by Straus' method on 2-bit windows. c0 and |c1| are
+// recoded into signed radix-4 digits a_i, r_i in {-1, 0, 1, 2} (sc_recode2) and ONE per-lane table holds the 11 points,
+// up to sign, that a digit pair can select, so a 2-bit window costs two doublings and one addition: per 4 bits the
+// same doublings, additions and conversions as verify_half_fu's two 4-bit tables, but 9 entries built per record
+// instead of 14 and 1,408 B of table per lane instead of 2,048.
+//   entry  1  2  3    4    5   6   7     8     9      10    11      (0: the identity)
+//   point  A  R  A+R  A-R  2A  2R  2A+R  A+2R  2A+2R  2A-R  2R-A
+enum {
+  kJtA = 1, kJtR, kJtApR, kJtAmR, kJt2A, kJt2R, kJt2ApR, kJtAp2R, kJt2Ap2R, kJt2AmR, kJt2RmA, kJointEntries
+};
+
+// Digit pair -> entry and sign. The key is (a + 1) | (r + 1) << 2, the two stored digits side by side; nibble `key` of
+// kJointIdx is the entry, bit `key` of kJointNeg says the pair selects the entry's negation.
+constexpr uint64_t joint_idx_table() {
+  // rows r = -1, 0, 1, 2; columns a = -1, 0, 1, 2
+  const int e[16] = {kJtApR,  kJtR, kJtAmR, kJt2AmR,   // r = -1: -(A+R), -R, A-R, 2A-R
+                     kJtA,    0,    kJtA,   kJt2A,     // r =  0: -A, 0, A, 2A
+                     kJtAmR,  kJtR, kJtApR, kJt2ApR,   // r =  1: -(A-R), R, A+R, 2A+R
+                     kJt2RmA, kJt2R, kJtAp2R, kJt2Ap2R};  // r = 2: 2R-A, 2R, A+2R, 2A+2R
+  uint64_t t = 0;
+  for (int k = 0; k < 16; ++k) t |= (uint64_t)e[k] << (4 * k);
+  return t;
+}
+constexpr uint64_t kJointIdx = joint_idx_table();
+constexpr uint32_t kJointNeg = 1u << 0 | 1u << 1 | 1u << 4 | 1u << 8;  // (-1,-1), (0,-1), (-1,0), (-1,1)
+
+// The joint table of decoded points A and R (Z = 1; R already negated when c1 < 0): 9 group operations, every operand
+// in a class the ladder already uses (tools/gen_fu.py check_group_law, "joint table"): mixed additions of a decoded or
+// converted point with a carried Niels form and its negation, doublings of a decoded or converted point.
+template <class TabJ>
+AT2V_HD AT2V_INLINE void build_joint_table(const gu_p3& A, const gu_p3& R, TabJ& tj) {
+  gu_cached c;
+  gu_p1p1 s;
+  gu_p3 Q, D;
+  gu_p2 q2;
+  gu_niels nA, nR, nn;
+  gu_cached_identity(c);
+  tj.store(0, c);
+  auto niels_of = [](gu_niels& n, const gu_cached& cc) {  // affine Niels form of a Z = 1 point from its cached form
+    n.ypx = cc.YpX;
+    fu_carry(n.ypx);
+    n.ymx = cc.YmX;
+    fu_carry(n.ymx);
+    n.xy2d = cc.T2d;  // 2d T = 2d x y, a carried product
+  };
+  auto put = [&](int e, const gu_p3& P) {
+    gu_p3_to_cached(c, P);
+    tj.store(e, c);
+  };
+  gu_p3_to_cached(c, A);
+  tj.store(kJtA, c);
+  niels_of(nA, c);
+  gu_p3_to_cached(c, R);
+  tj.store(kJtR, c);
+  niels_of(nR, c);
+  // A + R, then its double
+  gu_madd(s, A, nR);
+  gu_p1p1_to_p3(Q, s);
+  put(kJtApR, Q);
+  gu_p3_to_p2(q2, Q);
+  gu_p2_dbl(s, q2);
+  gu_p1p1_to_p3(Q, s);
+  put(kJt2Ap2R, Q);
+  // A - R
+  nn = nR;
+  gu_niels_cneg(nn, 1);
+  gu_madd(s, A, nn);
+  gu_p1p1_to_p3(Q, s);
+  put(kJtAmR, Q);
+  // 2A, 2A + R, 2A - R
+  gu_p3_to_p2(q2, A);
+  gu_p2_dbl(s, q2);
+  gu_p1p1_to_p3(D, s);
+  put(kJt2A, D);
+  gu_madd(s, D, nR);
+  gu_p1p1_to_p3(Q, s);
+  put(kJt2ApR, Q);
+  gu_madd(s, D, nn);
+  gu_p1p1_to_p3(Q, s);
+  put(kJt2AmR, Q);
+  // 2R, 2R + A, 2R - A
+  gu_p3_to_p2(q2, R);
+  gu_p2_dbl(s, q2);
+  gu_p1p1_to_p3(D, s);
+  put(kJt2R, D);
+  gu_madd(s, D, nA);
+  gu_p1p1_to_p3(Q, s);
+  put(kJtAp2R, Q);
+  gu_niels_cneg(nA, 1);
+  gu_madd(s, D, nA);
+  gu_p1p1_to_p3(Q, s);
+  put(kJt2RmA, Q);
+}
+
+// verify_half_fu with the joint table: the same checks, SHA-512, lattice reduction, t and B tables, the same group
+// element V (any evaluation of [c0]A + [c1]R gives it) and the same identity test, so the same verdicts.
+//   TabJ : store(e, gu_cached) / prefetch(stage, e, stage_just_read) / load_prefetched(stage, gu_cached)  (per lane,
+//          e in 0..11; two stages, window i's entry goes through stage i & 1)
+//   TabB0, TabB1 : as verify_half_fu; on the device they land in stages 0 and 1
+// An entry is requested right after the previous window's entry is read, so one addition, one conversion and the next
+// window's two doublings hide it, and nothing waits for it early. A B window (2-bit windows 0, 8, ..., 56: always stage
+// 0) gives both stages to the two B entries once its own entry is read, and requests the next window's entry when the
+// second B entry has been read.
+template <class TabJ, class TabB0, class TabB1, class MsgWord, class WaveMax, class Pace = NoPace>
+AT2V_HD AT2V_INLINE int verify_half_fu_joint(const uint32_t Rw[8], const uint32_t Aw[8], const uint32_t Sw[8],
+                                             uint32_t len, MsgWord msgword, int policy, TabJ& tj, const TabB0& tb0,
+                                             const TabB1& tb1, WaveMax wave_max, Pace&& pace = Pace()) {
+  // V1: s < l
+  int ok = sc_is_canonical(Sw);
+  if (policy == POLICY_LIBSODIUM_1_0_18) {
+    ok &= !enc_small_order(Rw);
+    ok &= enc_y_canonical(Aw) & !enc_small_order(Aw);
+  }
+  // V2: decode A and R; R must be canonical (y < p, not x = 0 with the sign bit)
+  gu_p3 A, R;
+  ok &= gu_frombytes(A, Aw);
+  ok &= gu_frombytes(R, Rw);
+  ok &= enc_y_canonical(Rw);
+  ok &= !(fu_iszero(R.X) & (int)(Rw[7] >> 31));
+  AT2V_PHASE(1);
+  pace.mark(10);
+  // V3: k = SHA-512(R || A || M) mod l
+  uint32_t k[8];
+  {
+    uint32_t pre[16];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      pre[i] = Rw[i];
+      pre[8 + i] = Aw[i];
+    }
+    uint64_t h[8];
+    sha512_msg<16>(h, pre, len, msgword);
+    uint32_t hw[16];
+    sha512_digest_words(hw, h);
+    sc_reduce512(k, hw);
+  }
+  AT2V_PHASE(5);
+  pace.mark(3);
+  HalfScalars hs;
+  lattice_reduce(hs, k);
+  AT2V_PHASE(7);
+  pace.mark(3);
+  uint32_t t[8];
+  sc_mul_signed(t, hs, Sw);
+  uint32_t c0d[8], c1d[8], td[8];
+  const int nd = sc_recode2_joint(c0d, c1d, hs.c0, hs.c1);
+  sc_recode16(td, t);
+  // 128 signed radix-4 digits hold values < 2^255 (the reduction keeps max(|c0|, |c1|) < 2^253); a lane
+  // that would need a 129th window fails closed
+  ok &= hs.bits <= 255;
+  const int nw_lane = ok ? nd : 0;
+  int nw = wave_max(nw_lane);
+  // B digits sit at windows 0, 8, ..., 56: the top window (no B digit) lies above them
+  constexpr int kNwMin = 58;
+  nw = nw < kNwMin ? kNwMin : nw;
+  AT2V_PHASE(2);
+  pace.mark(1);
+
+  if (hs.c1_neg) {
+    fu_neg(R.X, R.X, FU_KC);
+    fu_carry(R.X);
+    fu_neg(R.T, R.T, FU_KC);
+    fu_carry(R.T);
+  }
+  build_joint_table(A, R, tj);
+  AT2V_PHASE(3);
+  pace.mark(4);
+
+  // shared doubling chain over windows nw-1 .. 0:
+  //   acc = 4 acc + (a_i A + r_i (+-R)) + [8 | i, i < 64] (-t_{i/8} [2^(16 i/8)]B - t_{8+i/8} [2^(128+16 i/8)]B)
+  gu_p2 R2;
+  gu_p3 R3;
+  gu_p1p1 tt;
+  gu_cached ca;
+  gu_niels nb;
+  // the digit pair of window i, given the words that hold it
+  auto key2 = [](uint32_t wa, uint32_t wr, int i) -> uint32_t {
+    const int sh = 2 * (i & 15);
+    return ((wa >> sh) & 3u) | (((wr >> sh) & 3u) << 2);
+  };
+  auto entry_of = [](uint32_t key) -> int { return (int)((uint32_t)(kJointIdx >> (4 * key)) & 15u); };
+  auto neg_of = [](uint32_t key) -> int { return (int)((kJointNeg >> key) & 1u); };
+  int neg_cur, e_next, neg_next;
+  {
+    const int i = nw - 1;
+    const uint32_t k1 = key2(sel8(c0d, i >> 4), sel8(c1d, i >> 4), i);
+    const uint32_t k0 = key2(sel8(c0d, (i - 1) >> 4), sel8(c1d, (i - 1) >> 4), i - 1);
+    tj.prefetch(i & 1, entry_of(k1), false);
+    tj.prefetch((i - 1) & 1, entry_of(k0), false);
+    neg_cur = neg_of(k0);
+    gu_p3_identity(R3);
+    tj.load_prefetched(i & 1, ca);
+    gu_cached_cneg(ca, neg_of(k1));
+    gu_add(tt, R3, ca);
+    gu_p1p1_to_p2(R2, tt);
+  }
+  // The digit words live in a private array (see verify_half_fu, AT2V_DIGIT_AHEAD): the words of the NEXT window's pair
+  // are loaded at a window's start, after the pair they replace is extracted and before the pacing store and the
+  // prefetches, and first used a window later.
+  uint32_t wa = sel8(c0d, (nw - 3) >> 4), wr = sel8(c1d, (nw - 3) >> 4);
+  for (int i = nw - 2; i >= 0; --i) {
+    const bool bwin = (i & 7) == 0 && i < 64;  // a B window
+    {
+      const uint32_t kn = key2(wa, wr, i - 1);  // i = 0: window -1, unused
+      e_next = entry_of(kn);
+      neg_next = neg_of(kn);
+#if defined(__HIP_DEVICE_COMPILE__)
+      asm volatile("" ::"v"(e_next), "v"(neg_next) : "memory");  // they exist before the pacing store is issued
+#endif
+    }
+    if (i & 1) pace.window();  // one unit per 4 bits of ladder, as verify_half_fu
+    wa = sel8(c0d, (i - 2) >> 4);  // i < 2: index -1 selects word 0, unused
+    wr = sel8(c1d, (i - 2) >> 4);
+    uint32_t wt0 = 0, wt1 = 0;
+    if (bwin) {  // the words holding B digits i/8 and 8 + i/8
+      wt0 = sel8(td, i >> 4);
+      wt1 = sel8(td, 4 + (i >> 4));
+    }
+    gu_p2_dbl(tt, R2);
+    gu_p1p1_to_p2(R2, tt);
+    gu_p2_dbl(tt, R2);
+    gu_p1p1_to_p3(R3, tt);
+    tj.load_prefetched(i & 1, ca);
+    int e0 = 0, e1 = 0;
+    if (bwin) {  // -t digits: j = i/8 (table [j]B, stage 0) and 8 + i/8 (table [j 2^128]B, stage 1)
+      e0 = (1 << 15) - (int)((wt0 >> (16 * ((i >> 3) & 1))) & 0xffff);
+      e1 = (1 << 15) - (int)((wt1 >> (16 * ((i >> 3) & 1))) & 0xffff);
+      tb0.prefetch(e0 < 0 ? -e0 : e0);
+      tb1.prefetch(e1 < 0 ? -e1 : e1);
+    } else {
+      tj.prefetch((i - 1) & 1, e_next, false);  // (i odd or not a B window: i >= 1)
+    }
+    gu_cached_cneg(ca, neg_cur);
+    gu_add(tt, R3, ca);
+    if (bwin) {
+      gu_p1p1_to_p3(R3, tt);
+      tb0.load_prefetched(nb);
+      gu_niels_cneg(nb, e0 < 0);
+      gu_madd(tt, R3, nb);
+      gu_p1p1_to_p3(R3, tt);
+      tb1.load_prefetched(nb);
+      if (i > 0) tj.prefetch((i - 1) & 1, e_next, true);  // into stage 1, just read
+      gu_niels_cneg(nb, e1 < 0);
+      gu_madd(tt, R3, nb);
+    }
+    gu_p1p1_to_p2(R2, tt);
+    neg_cur = neg_next;
+  }
+  AT2V_PHASE(4);
+  // V == identity: X = 0 and Y = Z
+  fu d;
+  fu_sub(d, R2.Y, R2.Z, FU_KC);
+  return ok & fu_iszero(R2.X) & fu_iszero(d);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Two lanes per signature (the low-latency kernel). Side 0 owns A, side 1 owns R: each lane decodes
 // one point, builds one table, and runs its half of the shared-window chain,
 //   side 0: P0 = [c0]A - [t_lo]B          side 1: P1 = [c1]R - [t_hi 2^128]B   (t = t_lo + 2^128 t_hi),

@@ -239,6 +239,43 @@ def check_group_law(C, K):
         m.mul(z, t, nm + " Z"); m.mul(x, y, nm + " T")
     # --- cached form of a p3 point: YpX = Y + X, YmX = Y + K_C - X, Z2 = 2Z, T2d = T * 2d
     m.mul(C, C, "T2d", True)
+    # --- joint table (build_joint_table, at2v_verify_fu.h), the same sequence on per-limb maxima. A and R are decoded
+    #     points: X carried, Y < 2^255 in limbs, Z = 1, T a carried product, all <= C; R's negation is carried again.
+    def j_p3(p1p1, nm):                      # gu_p1p1_to_p3: four products, each a carried element
+        x, y, z, t = p1p1
+        m.mul(x, t, nm + " X"); m.mul(z, y, nm + " Y'", True); m.mul(z, t, nm + " Z"); m.mul(x, y, nm + " T")
+        return (C, C, C, C)
+
+    def j_cached(P, nm):                     # gu_p3_to_cached, then DevTabA::store carries and packs the four
+        m.mul(P[3], C, nm + " T2d", True)   # T * 2d (FU_D2 is a carried constant)
+        return (add(P[1], P[0]), add(P[1], KC), add(P[2], P[2]), C)
+
+    def j_niels(c):                          # niels_of: Y+X and Y-X carried, 2dT as it is
+        return (C, C, c[3])
+
+    def j_madd(P, n, nm):                    # gu_madd with the entry and with its negation (gu_niels_cneg)
+        X, Y, Z, T = P
+        ymj, ypj = add(Y, KC), add(Y, X)
+        assert dom(KC, X) and dom(KC, n[2])
+        for (pp, mm) in ((n[0], n[1]), (n[1], n[0])):
+            m.mul(ymj, mm, nm + " A", True); m.mul(ypj, pp, nm + " B", True)
+        m.mul(T, n[2], nm + " C", True); m.mul(T, KC, nm + " C-", True)
+        dj = add(Z, Z)
+        return (add(C, KC), add(C, C), add(dj, C), pcarry_even(add(dj, KC)))
+
+    def j_dbl(P, nm):                        # gu_p2_dbl of (X, Y, Z)
+        X, Y, Z = P[:3]
+        m.sq(X, nm + " XX", True); m.sq(Y, nm + " YY", True)
+        m.sq(add(X, Y), nm + " (X+Y)^2", True); m.sq(Z, nm + " 2Z^2", True, True)
+        return dbl
+
+    A = R = (C, C, C, C)
+    nA = j_niels(j_cached(A, "joint A")); nR = j_niels(j_cached(R, "joint R"))
+    S = j_p3(j_madd(A, nR, "joint A+-R"), "joint A+-R ->p3"); j_cached(S, "joint A+-R")
+    j_cached(j_p3(j_dbl(S, "joint 2(A+R)"), "joint 2(A+R) ->p3"), "joint 2(A+R)")
+    for (P, n, nm) in ((A, nR, "joint 2A"), (R, nA, "joint 2R")):
+        D = j_p3(j_dbl(P, nm), nm + " ->p3"); j_cached(D, nm)
+        j_cached(j_p3(j_madd(D, n, nm + "+-"), nm + "+- ->p3"), nm + "+-")
     # --- decode: u = y^2 + (p - 1), v = d y^2 + 1; checks on v x^2 -+ u
     u = add(C, K["PM1"])
     v = add(C, [1] + [0] * 9)
