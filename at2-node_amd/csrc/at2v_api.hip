@@ -140,30 +140,6 @@ struct StageSlot {
   size_t host_cap = 0;
   hsa_signal_t uploaded{0};  // the slot's DMA uploads: set to their count, each decrements it as it completes
 };
-// The staged form (test hook AT2V_TEST_STAGED=1, a context without a sender cache, a shard part above small_batch_max):
-// ONE launch of the persistent grid over the shard's whole part, issued before any record is uploaded; the records go up
-// in regions of 2^ushift records (>= 65,536, at most kMaxStageRegions) through the same slots and DMA uploads, and the
-// host publishes each landed region in a pinned word the waves poll (at2v_cache.h StagedArgs). Correct (the parity tests
-// run it), but slower than the chunk launches: 12.4-14.9 ms per 1M records against 11.0-11.7 (profiles/r06/r06o-r06v). The
-// device's clock follows its activity: a launch after 1 ms idle takes 10.5 ms instead of 9.6 (6 ms idle: 11.0, profiles/r06/r06u),
-// and a grid whose waves sleep while they wait for regions looks idle; chunk launches start only when their records are
-// up. Kept behind the hook for that measurement.
-struct StagedCtl {
-  unsigned long long ready;  // (epoch << 32) | regions published; bit 31 of the count: abort
-  uint32_t timeout;          // set by a wave that gave up waiting
-};
-struct StagedPlan {  // one shard's part of a host-buffer call in the staged form
-  bool active = false;
-  size_t m = 0, lo = 0;  // records, first record (absolute)
-  uint32_t ushift = 16, nreg = 0, submitted = 0, published = 0;
-  std::vector<size_t> at;  // region offsets in the pipe's arena
-  int slot_region[3] = {-1, -1, -1};
-  at2v::StagedArgs args{};
-  uint32_t* verdicts = nullptr;  // the call's device bitmap for this shard
-  bool launched = false;
-};
-constexpr size_t kStageRegionMinLog2 = 16;
-
 struct HostPipe {
   hipStream_t copy = nullptr;                 // the verdict download, (sharded) the all-gathers
   hipStream_t comp[2] = {nullptr, nullptr};   // verify launches of the chunks, alternating
@@ -177,8 +153,6 @@ struct HostPipe {
   bool pending = false;  // a chunk whose uploads are submitted and whose launch is not issued yet
   ChunkLaunch pend;
   uint64_t chunks = 0;  // chunks issued by this shard (slot chunks % kStageSlots, compute stream chunks % 2)
-  StagedCtl* ctl = nullptr;  // pinned, fine-grained (the staged form)
-  uint32_t epoch = 0;
 };
 
 struct Shard {
@@ -218,7 +192,6 @@ struct HostCall {
   size_t n = 0;
   std::vector<hipError_t> err;  // per shard
   std::vector<size_t> m;        // per shard: records
-  std::vector<char> staged;     // per shard: the staged form (its timeout word is checked)
   std::chrono::steady_clock::time_point t0;
 };
 
@@ -239,10 +212,6 @@ struct at2v_ctx {
   size_t stage_first = kStageFirstRecords, stage_max = kStageMaxRecords;
   unsigned copy_threads = 8;
   int pipe_streams = 0;     // create_comp_stream mode (test hook AT2V_TEST_PIPE_STREAMS)
-  bool staged = false;      // test hook AT2V_TEST_STAGED=1: the staged form where it applies (not faster, see StagedCtl)
-  uint32_t stage_nap = 2;   // StagedArgs.nap (test hook AT2V_TEST_STAGE_NAP)
-  uint32_t stage_launch_at = 0;  // test hook AT2V_TEST_STAGE_LAUNCH_AT: the launch once this many regions are published
-  bool stage_pre = false;   // test hook AT2V_TEST_STAGE_PRE: every region uploaded before the launch (kernel-only time)
   bool pipe_trace = false;  // test hook AT2V_TEST_PIPE_TRACE: per host-buffer call, where the host's time went (stderr)
   double tr_wait = 0, tr_copy = 0, tr_enq = 0;  // seconds, this call
   uint64_t host_chunks = 0;  // chunks staged by host-buffer calls (at2v_info.host_chunks)
@@ -543,11 +512,11 @@ bool scratch_ok(const Shard& s) {
 // after a compaction waits for it (cache_before_launch). The verdict words are zeroed first (fail closed).
 hipError_t launch_shard(at2v_ctx* ctx, Shard& s, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg,
                         uint32_t msg_bytes, const uint32_t* off, uint32_t n, uint32_t* verdicts, hipStream_t stream,
-                        bool zero_verdicts = true, bool pipeline = false, const at2v::StagedArgs* staged = nullptr) {
+                        bool zero_verdicts = true, bool pipeline = false) {
   // a chunk of the host-buffer pipeline whose batch is above small_batch_max: the throughput kernels at every chunk
   // size, with dense grids (launch_verify)
   const uint32_t pair_max = pipeline ? 0u : ctx->pair_max;
-  if (!verdicts || (!pk && !staged) || !scratch_ok(s)) return hipErrorInvalidValue;  // (never launch on a null buffer)
+  if (!verdicts || !pk || !scratch_ok(s)) return hipErrorInvalidValue;  // (never launch on a null buffer)
   if (ctx->test_fail_launches) {  // test hook: a launch failure, as a faulting device would report it
     --ctx->test_fail_launches;
     return hipErrorLaunchFailure;
@@ -583,7 +552,7 @@ hipError_t launch_shard(at2v_ctx* ctx, Shard& s, const uint8_t* pk, const uint8_
   if (e == hipSuccess)
     e = at2v::launch_verify(pk, sig, msg, msg_bytes, off, n, (int)ctx->policy, verdicts, (int4*)s.scratch[j].p,
                             (const int4*)s.btab.p, s.grid, pair_max, stream, c ? &ca : nullptr,
-                            part ? &pa : nullptr, pipeline ? 1 : 0, staged);
+                            part ? &pa : nullptr, pipeline ? 1 : 0);
   if (e == hipSuccess && c) {
     // claims of this launch -> payloads on the build stream (later launches use them; this one did not wait)
     e = hipEventRecord(c->claims_ready[cs], stream);
@@ -608,7 +577,6 @@ void free_pipe(Shard& s) {
     if (sl.host) (void)hipHostFree(sl.host);
     if (sl.uploaded.handle) (void)hsa_signal_destroy(sl.uploaded);
   }
-  if (p->ctl) (void)hipHostFree(p->ctl);
   for (DevBuf& b : p->arenas) b.release();
   for (hipEvent_t ev : p->comp_done)
     if (ev) (void)hipEventDestroy(ev);
@@ -632,18 +600,13 @@ hsa_status_t find_cpu_agent(hsa_agent_t a, void* data) {
 // A compute stream of the pipe. The two should sit on different hardware queues, or their launches run one after the
 // other and every chunk pays its own end-of-launch drain: HIP maps streams onto GPU_MAX_HW_QUEUES (4) shared queues, and
 // in a process with a few streams already the two new ones can land on the same queue (profiles/r06/r06d: queue 4 for
-// both). mode 0 (default): plain streams; 1: the second one at the highest priority (a queue of its own priority level);
-// 2: streams with a full CU mask (HIP gives a CU-masked stream a queue of its own). Test hook AT2V_TEST_PIPE_STREAMS.
-// Mode 1 was the default until the end of round 6: the high-priority queues stay with the process after their streams
-// are gone, and other processes on the GPU paid for them. Config 5 with a polluter process, run by a pytest process whose
-// earlier tests had used 8-shard host-buffer contexts: node queue p99 0.72-1.04 ms with mode 1, 0.48-0.60 ms with mode 0
-// (profiles/r06/r06ab, r06ad, r06ae). In a process with few streams the two modes run a 1M-record call alike (r06aa).
-hipError_t create_comp_stream(hipStream_t* st, int j, int mode, int device) {
-  if (mode == 1 && j == 1) {
-    int least = 0, greatest = 0;
-    hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-    return e == hipSuccess ? hipStreamCreateWithPriority(st, hipStreamNonBlocking, greatest) : e;
-  }
+// both). mode 0 (default): plain streams; 2: streams with a full CU mask (HIP gives a CU-masked stream a queue of its
+// own). Test hook AT2V_TEST_PIPE_STREAMS. Mode 1, the second stream at the highest priority (a queue of its own priority
+// level), was the default until the end of round 6 and is deleted: the high-priority queues stay with the process after
+// their streams are gone, and other processes on the GPU paid for them. Config 5 with a polluter process, run by a
+// pytest process whose earlier tests had used 8-shard host-buffer contexts: node queue p99 0.72-1.04 ms with it,
+// 0.48-0.60 ms with plain streams (profiles/r06/r06ab, r06ad, r06ae).
+hipError_t create_comp_stream(hipStream_t* st, int mode, int device) {
   if (mode == 2) {
     hipDeviceProp_t prop;
     hipError_t e = hipGetDeviceProperties(&prop, device);
@@ -662,7 +625,7 @@ hipError_t ensure_pipe(Shard& s, int mode) {
   s.pipe = p;
   hipError_t e = hipStreamCreateWithFlags(&p->copy, hipStreamNonBlocking);
   for (int j = 0; j < 2 && e == hipSuccess; ++j) {
-    e = create_comp_stream(&p->comp[j], j, mode, s.device);
+    e = create_comp_stream(&p->comp[j], mode, s.device);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&p->comp_done[j], hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventRecord(p->comp_done[j], p->copy);
   }
@@ -682,12 +645,6 @@ hipError_t ensure_pipe(Shard& s, int mode) {
   }
   for (StageSlot& sl : p->slot)
     if (e == hipSuccess) e = hsa_err(hsa_signal_create(0, 0, nullptr, &sl.uploaded));
-  if (e == hipSuccess)
-    e = hipHostMalloc((void**)&p->ctl, sizeof(StagedCtl), hipHostMallocCoherent | hipHostMallocMapped);
-  if (e == hipSuccess) {
-    p->ctl->ready = 0;
-    p->ctl->timeout = 0;
-  }
   if (e != hipSuccess) free_pipe(s);
   return e;
 }
@@ -883,160 +840,6 @@ hipError_t issue_chunk(at2v_ctx* ctx, Shard& s, at2v::CpuPool* copier, const uin
   return e;
 }
 
-// ---- the staged form (StagedPlan above) ----
-
-void stage_store(HostPipe& p, uint32_t count) {
-  __atomic_store_n(&p.ctl->ready, ((unsigned long long)p.epoch << 32) | count, __ATOMIC_RELEASE);
-}
-
-// Publish the regions whose uploads have landed, in order: those below `block_below` are waited for, later ones only if
-// already done. An upload error (negative signal) is returned; the caller aborts.
-hipError_t stage_publish(HostPipe& p, StagedPlan& sp, uint32_t block_below) {
-  const uint32_t before = sp.published;
-  hipError_t e = hipSuccess;
-  while (sp.published < sp.submitted) {
-    StageSlot& sl = p.slot[sp.published % kStageSlots];
-    if (sp.published >= block_below && hsa_signal_load_scacquire(sl.uploaded) > 0) break;
-    e = wait_uploads(sl);
-    if (e != hipSuccess) break;
-    ++sp.published;
-  }
-  if (sp.published != before) stage_store(p, sp.published);
-  return e;
-}
-
-// the single launch of a staged call, on comp[0]
-hipError_t stage_launch(at2v_ctx* ctx, Shard& s, StagedPlan& sp) {
-  HostPipe& p = *s.pipe;
-  const at2v::StagedArgs& sa = sp.args;
-  const size_t m = sp.m;
-  hipError_t e = launch_shard(ctx, s, (const uint8_t*)p.arena().p, nullptr, nullptr, 0, nullptr, (uint32_t)m,
-                              sp.verdicts, p.comp[0], /*zero_verdicts=*/false, /*pipeline=*/true, &sa);
-  if (e == hipSuccess) e = hipEventRecord(p.comp_done[0], p.comp[0]);
-  if (e != hipSuccess) sp.active = false;  // (nothing launched: nobody waits for the word)
-  sp.launched = e == hipSuccess;
-  return e;
-}
-
-// The call's launch for shard s (current device = s.device): layout of the regions in the arena, then the single launch
-// on comp[0]; its waves wait for the regions the host publishes.
-hipError_t stage_begin(at2v_ctx* ctx, Shard& s, StagedPlan& sp, size_t lo, size_t m, const uint32_t* msg_off,
-                       uint32_t* d_verdicts) {
-  HostPipe& p = *s.pipe;
-  for (StageSlot& sl : p.slot) (void)wait_uploads(sl);  // (after a failed call, uploads may still write the arena)
-  p.pending = false;
-  sp = StagedPlan{};
-  sp.active = true;
-  sp.verdicts = d_verdicts;
-  sp.lo = lo;
-  sp.m = m;
-  sp.ushift = kStageRegionMinLog2;
-  while (((m + ((size_t)1 << sp.ushift) - 1) >> sp.ushift) > (size_t)at2v::kMaxStageRegions) ++sp.ushift;
-  const size_t U = (size_t)1 << sp.ushift;
-  sp.nreg = (uint32_t)((m + U - 1) / U);
-  at2v::StagedArgs sa{};
-  size_t total = 0;
-  sp.at.resize(sp.nreg);
-  for (uint32_t u = 0; u < sp.nreg; ++u) {
-    const size_t a = lo + u * U, c = std::min(U, m - u * U);
-    const size_t mb = (size_t)(msg_off[a + c] - msg_off[a]);
-    sp.at[u] = total;
-    sa.mb[u] = (uint32_t)mb;
-    total += (chunk_layout(c, mb).total + 255) & ~(size_t)255;
-  }
-  hipError_t e = p.arena().ensure(total);
-  if (e != hipSuccess) return e;
-  for (uint32_t u = 0; u < sp.nreg; ++u) sa.at[u] = sp.at[u];
-  ++p.epoch;
-  p.ctl->timeout = 0;
-  stage_store(p, 0);
-  sa.ready = &p.ctl->ready;
-  sa.timeout = &p.ctl->timeout;
-  sa.epoch = p.epoch;
-  sa.ushift = sp.ushift;
-  sa.nreg = sp.nreg;
-  sa.last_c = (uint32_t)(m - (size_t)(sp.nreg - 1) * U);
-  sa.nap = ctx->stage_nap;
-  sp.args = sa;
-  if (ctx->stage_pre || ctx->stage_launch_at) return hipSuccess;  // (stage_launch later)
-  return stage_launch(ctx, s, sp);
-}
-
-// Region u of the plan: host copy into its slot (after the slot's previous region has landed and been published), DMA
-// uploads into the arena; between copy batches, the regions that have landed are published. Region 0 is published as
-// soon as it lands (the launch's waves are waiting for it).
-hipError_t stage_region(at2v_ctx* ctx, Shard& s, at2v::CpuPool* copier, StagedPlan& sp, const uint8_t* pk,
-                        const uint8_t* sig, const uint8_t* msg, const uint32_t* msg_off) {
-  HostPipe& p = *s.pipe;
-  const uint32_t u = sp.submitted;
-  const size_t U = (size_t)1 << sp.ushift;
-  const size_t a = sp.lo + u * U, c = std::min(U, sp.m - u * U);
-  const uint32_t mb0 = msg_off[a];
-  const size_t mb = (size_t)(msg_off[a + c] - mb0);
-  const ChunkLayout L = chunk_layout(c, mb);
-  const int k = (int)(u % kStageSlots);
-  StageSlot& sl = p.slot[k];
-  using clk = std::chrono::steady_clock;
-  const auto t0 = clk::now();
-  hipError_t e = stage_publish(p, sp, u >= kStageSlots ? u - kStageSlots + 1 : 0);  // the slot's previous region
-  if (e == hipSuccess && sl.host_cap < L.total) {
-    if (sl.host) (void)hipHostFree(sl.host);
-    sl.host = nullptr;
-    sl.host_cap = 0;
-    const size_t want = std::max(L.total + L.total / 4, chunk_layout(U, 0).total + U * 128);
-    e = hipHostMalloc((void**)&sl.host, want, hipHostMallocDefault);
-    if (e == hipSuccess) sl.host_cap = want;
-  }
-  if (e != hipSuccess) return e;
-  const auto t1 = clk::now();
-  uint8_t* d = (uint8_t*)p.arena().p + sp.at[u];
-  hsa_signal_store_screlease(sl.uploaded, mb ? 3 : 2);
-  auto upload = [&](size_t at, size_t len) {
-    return hsa_err(hsa_amd_memory_async_copy(d + at, p.gpu, sl.host + at, p.cpu, len, 0, nullptr, sl.uploaded));
-  };
-  hipError_t ep = hipSuccess;
-  auto poll = [&]() {
-    if (ep == hipSuccess) ep = stage_publish(p, sp, 0);
-  };
-  CopyJob job;
-  job.add(sl.host, pk + a * 32, c * 32);
-  run_copy(copier, job, c * 32, poll);
-  e = upload(0, c * 32);
-  job.add(sl.host + L.sig, sig + a * 64, c * 64);
-  job.add_offsets((uint32_t*)(sl.host + L.off), msg_off + a, c + 1, mb0);
-  run_copy(copier, job, c * 68, poll);
-  if (e == hipSuccess) e = upload(L.sig, L.msg - L.sig);
-  if (mb) {
-    job.add(sl.host + L.msg, msg + mb0, mb);
-    run_copy(copier, job, mb, poll);
-    if (e == hipSuccess) e = upload(L.msg, mb);
-  }
-  if (e != hipSuccess) {
-    hsa_signal_store_screlease(sl.uploaded, 0);
-    return e;
-  }
-  sp.submitted = u + 1;
-  sp.slot_region[k] = (int)u;
-  const auto t2 = clk::now();
-  e = ep;
-  const uint32_t la = std::min(ctx->stage_launch_at, sp.nreg);
-  if (e == hipSuccess) e = stage_publish(p, sp, u == 0 ? 1 : (!ctx->stage_pre && u + 1 == la ? la : 0));
-  if (e == hipSuccess && !ctx->stage_pre && !sp.launched && la && sp.published >= la) e = stage_launch(ctx, s, sp);
-  ++p.chunks;
-  ++ctx->host_chunks;
-  if (ctx->pipe_trace) {
-    const auto t3 = clk::now();
-    ctx->tr_wait += std::chrono::duration<double>(t1 - t0).count() + std::chrono::duration<double>(t3 - t2).count();
-    ctx->tr_copy += std::chrono::duration<double>(t2 - t1).count();
-  }
-  return e;
-}
-
-// a failed staged call: the launch's waves stop waiting (their chunks' verdicts are 0; the call reports the error)
-void stage_abort(HostPipe& p, StagedPlan& sp) {
-  if (sp.active) stage_store(p, 0x80000000u);
-}
-
 // The pipe's arena for a shard's part of a call (m records, mb message bytes), before its first chunk: every launch of
 // the previous host-buffer call has completed (the call waited for its verdict copy, which followed them).
 hipError_t begin_arena(at2v_ctx* ctx, Shard& s, size_t m, size_t mb) {
@@ -1176,10 +979,6 @@ int at2v_create(const at2v_opts* opts, at2v_ctx** out) {
   c->copy_threads = (unsigned)at2v::test_env_long("AT2V_TEST_COPY_THREADS", 8);
   c->pipe_streams = (int)at2v::test_env_long("AT2V_TEST_PIPE_STREAMS", c->pipe_streams);
   c->pipe_trace = at2v::test_env_long("AT2V_TEST_PIPE_TRACE", 0) != 0;
-  c->staged = at2v::test_env_long("AT2V_TEST_STAGED", 0) != 0;
-  c->stage_nap = (uint32_t)at2v::test_env_long("AT2V_TEST_STAGE_NAP", 2);
-  c->stage_pre = at2v::test_env_long("AT2V_TEST_STAGE_PRE", 0) != 0;
-  c->stage_launch_at = (uint32_t)at2v::test_env_long("AT2V_TEST_STAGE_LAUNCH_AT", 0);
   if (c->stage_first < 64) c->stage_first = 64;
   if (c->stage_max < c->stage_first) c->stage_max = c->stage_first;
   c->pair_max = o.small_batch_max == 0 ? AT2V_SMALL_BATCH_DEFAULT
@@ -1275,12 +1074,10 @@ void host_call_issue(at2v_ctx* ctx, int k) {
   const size_t n = hc.n, G = ctx->shards.size();
   at2v::CpuPool* copier = copy_pool(ctx);
   std::vector<ChunkPlan> plan(G);
-  std::vector<StagedPlan> stp(G);
   std::vector<size_t> lo(G);
   std::vector<hipError_t>& err = hc.err;
   err.assign(G, hipSuccess);
   hc.m.assign(G, 0);
-  hc.staged.assign(G, 0);
   hc.t0 = std::chrono::steady_clock::now();
   ctx->tr_wait = ctx->tr_copy = ctx->tr_enq = 0;
   for (size_t g = 0; g < G; ++g) {
@@ -1294,12 +1091,7 @@ void host_call_issue(at2v_ctx* ctx, int k) {
     if (e == hipSuccess) e = s.hverdict[k].ensure(((r.size() + 31) / 32) * 4);
     if (e == hipSuccess) e = ensure_pipe(s, ctx->pipe_streams);
     if (e == hipSuccess) s.pipe->cur = k;
-    if (e == hipSuccess && ctx->staged && !s.cache && r.size() > ctx->pair_max) {
-      e = stage_begin(ctx, s, stp[g], r.lo, r.size(), msg_off, (uint32_t*)s.hverdict[k].p);
-      hc.staged[g] = 1;
-    } else if (e == hipSuccess) {
-      e = begin_arena(ctx, s, r.size(), (size_t)(msg_off[r.hi] - msg_off[r.lo]));
-    }
+    if (e == hipSuccess) e = begin_arena(ctx, s, r.size(), (size_t)(msg_off[r.hi] - msg_off[r.lo]));
     err[g] = e;
   }
   for (bool more = true; more;) {
@@ -1307,14 +1099,6 @@ void host_call_issue(at2v_ctx* ctx, int k) {
     for (size_t g = 0; g < G; ++g) {
       if (err[g] != hipSuccess) continue;
       Shard& s = ctx->shards[g];
-      if (stp[g].active) {
-        StagedPlan& sp = stp[g];
-        if (sp.submitted >= sp.nreg) continue;
-        err[g] = hipSetDevice(s.device);
-        if (err[g] == hipSuccess) err[g] = stage_region(ctx, s, copier, sp, pk, sig, msg, msg_off);
-        more = more || sp.submitted < sp.nreg;
-        continue;
-      }
       ChunkPlan& cp = plan[g];
       if (cp.done()) continue;
       const size_t at = cp.pos, c = cp.take();
@@ -1325,18 +1109,12 @@ void host_call_issue(at2v_ctx* ctx, int k) {
       more = more || !cp.done();
     }
   }
-  for (size_t g = 0; g < G; ++g) {  // the last chunk of every shard / every staged region published
+  for (size_t g = 0; g < G; ++g) {  // the last chunk of every shard
     Shard& s = ctx->shards[g];
     if (plan[g].m == 0 || !s.pipe) continue;
     hipError_t e = hipSetDevice(s.device);
-    if (e == hipSuccess && stp[g].active && err[g] == hipSuccess) {
-      e = stage_publish(*s.pipe, stp[g], stp[g].submitted);
-      if (e == hipSuccess && !stp[g].launched) e = stage_launch(ctx, s, stp[g]);
-    } else if (e == hipSuccess && !stp[g].active) {
-      e = flush_chunk(ctx, s);
-    }
+    if (e == hipSuccess) e = flush_chunk(ctx, s);
     if (err[g] == hipSuccess) err[g] = e;
-    if (err[g] != hipSuccess) stage_abort(*s.pipe, stp[g]);
   }
   // the verdict words of each shard, once its last two launches are done (copy stream)
   for (size_t g = 0; g < G; ++g) {
@@ -1368,8 +1146,6 @@ void host_call_finish(at2v_ctx* ctx, int k) {
     Shard& s = ctx->shards[g];
     if (hc.m[g] == 0 || hc.err[g] != hipSuccess || hipSetDevice(s.device) != hipSuccess) continue;
     hipError_t e = hipEventSynchronize(s.hcopied[k]);
-    if (e == hipSuccess && hc.staged[g] && __atomic_load_n(&s.pipe->ctl->timeout, __ATOMIC_ACQUIRE))
-      e = hipErrorLaunchTimeOut;  // (a wave gave up waiting for a region: its chunks' verdicts are 0)
     if (e != hipSuccess && rc == AT2V_OK) rc = hip_code(e);
   }
   if (ctx->pipe_trace)
@@ -1428,7 +1204,6 @@ int at2v_verify_batch_submit(at2v_ctx* ctx, const uint8_t* pk, const uint8_t* si
   (void)hipGetDevice(&prev);
   host_call_finish(ctx, k);  // the call two tickets back: its slot's bitmaps and arenas are reused (its result is lost
                              // unless waited for; at most two calls are in flight)
-  if (ctx->staged) drain_host_calls(ctx);  // (the staged form's ready word serves one call at a time)
   hc = HostCall{};
   hc.active = true;
   hc.ticket = t;

@@ -68,58 +68,12 @@ struct Pace {
 // instead of 64 consecutive records: with kCache ([j]A tables) the hit list's chunks (every record cached: A's decode and
 // table skipped) and then the miss list's, without it the miss list alone (the comb kernel takes the hits). A record's
 // verdict bit is set by an atomic OR (the lists are in no particular order; the launcher zeroed the words).
-// kStaged (StagedArgs, the host pipeline's single launch): record i of region u = i >> ushift is read from the region's
-// own layout once the host has published the region (stage_wait); a wave that cannot get it (abort, time limit) stores
-// zero verdict words for its chunks.
-constexpr unsigned long long kStageTimeoutTicks = 1000000000ull;  // 10 s of the 100 MHz s_memrealtime clock
-
-// lane 0 polls the published region count until it exceeds `need` - 1; returns it (wave-uniform), or 0 on abort / time
-// limit (then *dead)
-__device__ AT2V_INLINE uint32_t stage_wait(const StagedArgs* sp, uint32_t need, int lane, bool& dead) {
-  int got = 0;
-  if (lane == 0) {
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    for (;;) {
-      const unsigned long long v = __hip_atomic_load(sp->ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      const uint32_t cnt = (uint32_t)v;
-      if ((uint32_t)(v >> 32) == sp->epoch) {
-        if (cnt & 0x80000000u) {
-          got = -1;
-          break;
-        }
-        if (cnt >= need) {
-          got = (int)cnt;
-          break;
-        }
-      }
-      if (__builtin_amdgcn_s_memrealtime() - t0 > kStageTimeoutTicks) {
-        __hip_atomic_store(sp->timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        got = -1;
-        break;
-      }
-      for (uint32_t z = 0; z < sp->nap; ++z) __builtin_amdgcn_s_sleep(8);
-    }
-  }
-  got = __builtin_amdgcn_readfirstlane(got);
-#ifndef AT2V_STAGE_FENCE
-#define AT2V_STAGE_FENCE 2  // after every poll: 1 a system-scope acquire, 2 a workgroup-scope one (L1), 0 none
-#endif
-#if AT2V_STAGE_FENCE == 1
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");  // system scope
-#elif AT2V_STAGE_FENCE == 2
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-#endif
-  dead = got < 0;
-  return got < 0 ? 0u : (uint32_t)got;
-}
-
-template <bool kCache, bool kPart = false, bool kStaged = false>
+template <bool kCache, bool kPart = false>
 __device__ AT2V_INLINE void verify_chunks(
     int4* astage, int4* rstage, const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig,
     const uint8_t* __restrict__ msg, uint32_t msg_total, const uint32_t* __restrict__ off, uint32_t n, int policy,
     uint32_t* __restrict__ verdicts, int4* __restrict__ scratch, const int4* __restrict__ btab,
-    uint32_t* __restrict__ chunk_queue, const CacheArgs* cp,
-    const PartArgs* pp = nullptr, const StagedArgs* sp = nullptr) {
+    uint32_t* __restrict__ chunk_queue, const CacheArgs* cp, const PartArgs* pp = nullptr) {
   const int lane = threadIdx.x & 63;
   const int wib = AT2V_UNIFORM(threadIdx.x >> 6);  // wave-uniform: the LDS stage addresses live in SGPRs
   const uint32_t wave = blockIdx.x * kWavesPerBlock + wib;
@@ -154,9 +108,6 @@ __device__ AT2V_INLINE void verify_chunks(
   constexpr uint32_t kHalf = kWavesPerBlock / 2;
   const uint32_t c_first = wib < (int)kHalf ? blockIdx.x * kHalf + wib
                                             : gridDim.x * kHalf + blockIdx.x * kHalf + (wib - kHalf);
-  const uint8_t* const arena = pk;  // kStaged: the launch passes its arena as pk
-  uint32_t known = 0;  // kStaged: regions this wave has seen published
-  bool dead = false;   // kStaged: the regions it waits for will not come
   for (uint32_t c = c_first; c < nchunks;) {
     AT2V_PHASE(0);
 #ifdef AT2V_WAIT_PROBE
@@ -177,20 +128,6 @@ __device__ AT2V_INLINE void verify_chunks(
       i = c * 64 + lane;
       ii = i < n ? i : n - 1;  // tail lanes recompute a real record; their bit is masked
       act = i < n;
-    }
-    int skip = 0;  // kStaged: the chunk's region never came (verdicts 0)
-    if constexpr (kStaged) {  // the chunk's region (wave-uniform: regions are multiples of 64 records)
-      const uint32_t u0 = (c * 64) >> sp->ushift, u = u0 < sp->nreg - 1 ? u0 : sp->nreg - 1;
-      if (u >= known && !dead) known = stage_wait(sp, u + 1, lane, dead);
-      skip = u >= known ? 1 : 0;
-      const uint8_t* b = arena + sp->at[u];
-      const uint32_t rc = u == sp->nreg - 1 ? sp->last_c : 1u << sp->ushift;
-      pk = b;
-      sig = b + (size_t)rc * 32;
-      off = reinterpret_cast<const uint32_t*>(b + (size_t)rc * 96);
-      msg = b + (((size_t)rc * 96 + ((size_t)rc + 1) * 4 + 15) & ~(size_t)15);
-      msg_total = sp->mb[u];
-      ii -= u << sp->ushift;
     }
     uint32_t Rw[8], Sw[8], Aw[8];
     load8(Rw, sig + (size_t)ii * 64);
@@ -240,9 +177,7 @@ __device__ AT2V_INLINE void verify_chunks(
       DevTabA tc{ta};
       if (all_hit) tc.base = cc.payload + (size_t)u * kTabAGranules;
       good = verify_half_fu<true>(Rw, Aw, Sw, len, msgword, policy, tc, tr, tb0, tb1, wmax, pace, all_hit, a_ok) & act;
-    } else if (skip) {
-      good = 0;
-    } else if constexpr (!kCache && !kPart && !kStaged) {
+    } else if constexpr (!kCache && !kPart) {
       // verify_kernel: nothing comes from a sender cache, so A and R share one joint table (the slot's first 88 granules)
       DevTabJ tj{ta, (int)(tr.stage - ta.stage)};
       good = verify_half_fu_joint(Rw, Aw, Sw, len, msgword, policy, tj, tb0, tb1, wmax, pace) & act;
@@ -284,21 +219,6 @@ __global__ __launch_bounds__(kBlock, kVerifyWavesPerSimd) void verify_kernel(
 }
 
 // the same with the per-sender A cache (at2v_opts.sender_cache, tables [j]A)
-// the host pipeline's single launch over a batch still being uploaded (StagedArgs)
-__global__ __launch_bounds__(kBlock, kVerifyWavesPerSimd) void verify_kernel_staged(
-    const uint8_t* __restrict__ arena, uint32_t n, int policy, uint32_t* __restrict__ verdicts,
-    int4* __restrict__ scratch, const int4* __restrict__ btab,
-    uint32_t* __restrict__ chunk_queue, StagedArgs sa) {
-  __shared__ int4 astage[kWavesPerBlock * 10 * 64];
-  __shared__ int4 rstage[kWavesPerBlock * 10 * 64];
-  // one system-scope acquire per block before any wave reads a region: no cache keeps a line of the arena from an
-  // earlier launch (the regions are re-uploaded at the same addresses every call)
-  if (threadIdx.x < 64) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-  __syncthreads();
-  verify_chunks<false, false, true>(astage, rstage, arena, arena, arena, 0, nullptr, n, policy, verdicts, scratch, btab,
-                                    chunk_queue, nullptr, nullptr, &sa);
-}
-
 __global__ __launch_bounds__(kBlock, kVerifyWavesPerSimd) void verify_kernel_cached(
     const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msg,
     uint32_t msg_total, const uint32_t* __restrict__ off, uint32_t n, int policy, uint32_t* __restrict__ verdicts,
@@ -494,7 +414,7 @@ size_t part_bytes_per_record() { return 12; }  // hidx, hinfo, midx
 hipError_t launch_verify(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, uint32_t msg_total,
                          const uint32_t* off, uint32_t n, int policy, uint32_t* verdicts, int4* scratch,
                          const int4* btab, int grid, uint32_t pair_max, hipStream_t stream,
-                         const CacheArgs* cache, const PartArgs* part, int dense, const StagedArgs* staged) {
+                         const CacheArgs* cache, const PartArgs* part, int dense) {
   if (n == 0) return hipSuccess;
   if (n <= pair_max && !(cache && cache->comb)) {  // (with combs, small batches take the comb kernel: faster still)
     // one wave (32 records) per SIMD: 4-wave blocks; the context's scratch holds grid x 8 waves of (larger) slots
@@ -523,12 +443,6 @@ hipError_t launch_verify(const uint8_t* pk, const uint8_t* sig, const uint8_t* m
   if (!lat_comb && !parted) {
     const hipError_t me = hipMemsetAsync(queue, 0, sizeof(uint32_t), stream);
     if (me != hipSuccess) return me;
-  }
-  if (staged) {  // the whole persistent grid: the records arrive while it runs
-    if (cache) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(verify_kernel_staged, dim3(grid), dim3(kBlock), 0, stream, pk, n, policy, verdicts, scratch,
-                       btab, queue, *staged);
-    return hipGetLastError();
   }
   if (cache && part && n > pair_max) {
     // partitioned (at2v_cache.h PartArgs): classify -> (combs) hit list by comb additions -> ladder over the rest. The

@@ -14,12 +14,11 @@ namespace at2v {
 // ---- verify
 // One batch on `stream`: n <= pair_max takes a low-latency kernel, larger launches the persistent grid of `grid` blocks
 // (scratch: scratch_bytes(grid); btab: btab_bytes(), built by launch_build_btab). cache: the per-sender A cache is on
-// (part: the launch classifies its records first and verifies hits and misses apart); dense: fill every block;
-// staged: the host pipeline's single launch over records still being uploaded (pk = the arena).
+// (part: the launch classifies its records first and verifies hits and misses apart); dense: fill every block.
 hipError_t launch_verify(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, uint32_t msg_total,
                          const uint32_t* off, uint32_t n, int policy, uint32_t* verdicts, int4* scratch,
                          const int4* btab, int grid, uint32_t pair_max, hipStream_t stream,
-                         const CacheArgs* cache, const PartArgs* part, int dense, const StagedArgs* staged);
+                         const CacheArgs* cache, const PartArgs* part, int dense);
 hipError_t verify_occupancy(int* blocks_per_cu, int* vgprs);
 int block_threads();
 size_t scratch_bytes_per_block();

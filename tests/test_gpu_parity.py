@@ -294,20 +294,19 @@ def test_config3_total_size_on_one_gpu(at2v_mod):
 
 
 # ---- the host-buffer path's pipeline (at2v_api.hip HostPipe; round 6) ----
-# The staged form (test hook AT2V_TEST_STAGED=1): one launch over the shard's part, records uploaded in regions of 65,536
-# that the waves wait for. Sizes: one region (32,833 records), two (the second ragged), seven (every staging slot reused).
-# The chunked form (the default): the first chunks are 65,536 records,
-# later ones 131,072, and a remainder below the first chunk's size joins the chunk before it; its two compute streams
-# are created each way (AT2V_TEST_PIPE_STREAMS: one hardware queue or two, so consecutive launches overlap or not).
-@pytest.mark.parametrize("form", ["staged", "chunked-plain", "chunked-priority", "chunked-cumask"])
+# Chunk launches alternating over two compute streams: the first two chunks are 65,536 records, later ones 131,072, and
+# a remainder below the first chunk's size joins the chunk before it. Sizes: one chunk (32,833 records), one merged chunk
+# with a ragged tail (98,437), four chunks (400,009: every staging slot reused). The two compute streams are created each
+# way (AT2V_TEST_PIPE_STREAMS: plain streams, or CU-masked ones that get a hardware queue each, so consecutive launches
+# overlap or not).
+@pytest.mark.parametrize("form", ["chunked-plain", "chunked-cumask"])
 @pytest.mark.parametrize("n", [32_833, 98_437, 400_009])
 def test_host_pipeline_chunks_adversarial(at2v_mod, oracle, monkeypatch, n, form):
     """at2v_verify_batch through each form of the pipeline. Adversarial records, record by record against the oracle,
     twice through one context (the second call reuses its staging slots and device arena); a sentinel word after the
     bitmap stays untouched and the pad bits of the last word are 0"""
-    monkeypatch.setenv("AT2V_TEST_STAGED", "1" if form == "staged" else "0")
     streams = form.split("-")[-1]
-    monkeypatch.setenv("AT2V_TEST_PIPE_STREAMS", {"staged": "0", "plain": "0", "priority": "1", "cumask": "2"}[streams])
+    monkeypatch.setenv("AT2V_TEST_PIPE_STREAMS", {"plain": "0", "cumask": "2"}[streams])
     pk, sig, msg, off, cls = oracle.gen_adversarial(CFG_SEED + 101, 0, n, 72)
     want = oracle.verify_batch(pk, sig, msg, off)
     lib = at2v_mod.load_library()
@@ -324,12 +323,12 @@ def test_host_pipeline_chunks_adversarial(at2v_mod, oracle, monkeypatch, n, form
                 assert int(words[(n - 1) // 32]) >> (n % 32) == 0
 
 
-def test_host_pipeline_staged_alternating_batches(at2v_mod, monkeypatch):
-    """The staged form reads each region as soon as the host publishes it, from DMA-written device memory the previous
-    call's launch also read (same arena, same addresses). Two batches of 1,000,003 records (16 regions, the last one
-    ragged) alternate through one context six times: A every record valid, B the same with an S byte flipped in 5,000
-    records. Any stale line of the other batch would flip verdicts: exactly B's mutated records are rejected each time,
-    and the pad bits stay 0"""
+def test_host_pipeline_alternating_batches(at2v_mod):
+    """Every call's chunks are uploaded by DMA into the device memory the previous call's launches also read (same arena,
+    same addresses). Two batches of 1,000,003 records (chunks of 65,536, 65,536, then 131,072 each, the remainder merged
+    into the last) alternate through one context six times: A every record valid, B the same with an S byte flipped in
+    5,000 records. Any stale line of the other batch would flip verdicts: exactly B's mutated records are rejected each
+    time, and the pad bits stay 0"""
     import torch
     n, L = 1_000_003, 100
     with at2v_mod.BatchVerifier() as g:
@@ -350,7 +349,6 @@ def test_host_pipeline_staged_alternating_batches(at2v_mod, monkeypatch):
     sig_b = sig_a.copy()
     sig_b[idx, 32 + rng.integers(0, 31, idx.size)] ^= 0x04
     lib = at2v_mod.load_library()
-    monkeypatch.setenv("AT2V_TEST_STAGED", "1")
     with at2v_mod.BatchVerifier() as v:
         for rep in range(6):
             sig = sig_b if rep % 2 else sig_a

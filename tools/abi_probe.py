@@ -4,7 +4,7 @@ variants, for tuning the HostPipe staging (at2v_api.hip). Each variant sets the 
 AT2V_TEST_STAGE_MAX / AT2V_TEST_COPY_THREADS (AT2V_TEST_HOOKS=1) before creating its context; variants alternate over
 `--rounds` rounds so box drift hits them alike. Also prints the device-API kernel time of the same batch and a
 single-thread numpy copy rate of the batch (host memory bandwidth).
-usage: python tools/abi_probe.py [--n 1048576] [--calls 8] [--rounds 2] [--variants first:max:threads[:streams[:staged]],...]
+usage: python tools/abi_probe.py [--n 1048576] [--calls 8] [--rounds 2] [--variants first:max:threads[:streams],...]
 -> one JSON line"""
 import argparse
 import json
@@ -123,9 +123,8 @@ def main():
     out = {"n": n, "kernel_ms_after_gap": gaps, "kernel_ms_device_api": kernel_ms, "kernel_ms_device_api_cold": cold_ms, "device_api_split_ms": subs, "numpy_copy_gbs_1thread": copy_gbs, "variants": {}}
     for r in range(a.rounds):
         for var in a.variants.split(","):
-            first, mx, th, ps, st = (var.split(":") + ["1", "0"])[:5]
-            os.environ["AT2V_TEST_PIPE_STREAMS"] = ps
-            os.environ["AT2V_TEST_STAGED"] = st  # 1: the staged single launch, 0: chunk launches
+            first, mx, th, ps = (var.split(":") + ["0"])[:4]
+            os.environ["AT2V_TEST_PIPE_STREAMS"] = ps  # 0: plain compute streams, 2: CU-masked ones
             os.environ["AT2V_TEST_STAGE_FIRST"] = first
             os.environ["AT2V_TEST_STAGE_MAX"] = mx
             os.environ["AT2V_TEST_COPY_THREADS"] = th

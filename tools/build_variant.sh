@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build a libat2v variant with extra kernel defines for in-process A/B runs (tools/ab_bench.py):
 #   tools/build_variant.sh <tag> -DAT2V_COMB_PROBE ...
-# The kernels keep only their measuring switches (AT2V_COMB_PROBE, AT2V_WAIT_PROBE, AT2V_STAGE_FENCE) and the shared
+# The kernels keep only their measuring switches (AT2V_COMB_PROBE, AT2V_WAIT_PROBE) and the shared
 # headers' arithmetic switches (e.g. -DAT2V_TAB_MADD=0); any other variant is made by editing the source first
 # (DESIGN.md "Retired build switches").
 # -> at2-node_amd/at2v/variants/libat2v_<tag>.so (the API/host objects are the product's own)
