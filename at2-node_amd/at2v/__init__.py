@@ -32,6 +32,8 @@ _POLICIES = {"dalek": POLICY_DALEK_V1, "dalek_v1": POLICY_DALEK_V1, "libsodium":
 # must match include/at2v.h (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = ("at2v_abi_version", "at2v_create", "at2v_destroy", "at2v_verify_batch", "at2v_verify_batch_device",
                     "at2v_verify_one", "at2v_verify_one_policy", "at2v_strerror", "at2v_gen_records_device",
+                    "at2v_reject_reasons", "at2v_reject_reasons_device", "at2v_verify_one_reason", "at2v_reason_name",
+                    "at2v_queue_poll_reasons",
                     "at2v_gen_records_senders_device", "at2v_gen_records_keys_device", "at2v_sign_batch", "at2v_get_info", "at2v_decode_points",
                     "at2v_comm_get_unique_id", "at2v_comm_init_rank", "at2v_verify_shard_gather_device",
                     "at2v_verify_batch_sharded", "at2v_verify_batch_submit", "at2v_verify_batch_wait",
@@ -49,11 +51,27 @@ class At2vError(RuntimeError):
         self.code = code
 
 
+# include/at2v.h at2v_reason: why a record was rejected (0 = it was not)
+REASON_VALID, REASON_A_DECODE, REASON_S_RANGE, REASON_A_POLICY, REASON_R_POLICY, REASON_R_ENCODING, REASON_EQUATION = \
+    range(7)
+REASON_UNKNOWN = 0xFF  # the call or the batch failed: neither valid nor invalid
+
+
+def reason_name(reason: int) -> str:
+    """at2v_reason_name: a short description of an at2v_reason"""
+    return load_library().at2v_reason_name(int(reason)).decode()
+
+
 class VerifyError(Exception):
-    """Signature rejected (drop::crypto::sign::VerifyError)."""
+    """Signature rejected (drop::crypto::sign::VerifyError). `reason` is the at2v_reason (REASON_*): 1 is what the
+    reference answers with InvalidArgument at ingest (an undecodable sender key), 2..6 a payload never delivered."""
+
+    def __init__(self, message: str = "signature verification failed", reason: int = REASON_UNKNOWN):
+        super().__init__(message)
+        self.reason = reason
 
 
-ABI_VERSION = 7  # include/at2v.h AT2V_ABI_VERSION: the struct layouts below are those of this version
+ABI_VERSION = 8  # include/at2v.h AT2V_ABI_VERSION: the struct layouts below are those of this version
 E_PEER = -7      # AT2V_E_PEER: another rank of the communicator failed this collective batch
 
 
@@ -154,6 +172,14 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.at2v_get_info.restype = ctypes.c_int
     lib.at2v_decode_points.argtypes = [P, P, ctypes.c_size_t, P]
     lib.at2v_decode_points.restype = ctypes.c_int
+    lib.at2v_reject_reasons.argtypes = [P, P, P, ctypes.c_size_t, P, P]
+    lib.at2v_reject_reasons.restype = ctypes.c_int
+    lib.at2v_reject_reasons_device.argtypes = [P, P, P, ctypes.c_size_t, P, P, P]
+    lib.at2v_reject_reasons_device.restype = ctypes.c_int
+    lib.at2v_verify_one_reason.argtypes = [P, P, P, ctypes.c_size_t, ctypes.c_int]
+    lib.at2v_verify_one_reason.restype = ctypes.c_int
+    lib.at2v_reason_name.argtypes = [ctypes.c_int]
+    lib.at2v_reason_name.restype = ctypes.c_char_p
     from . import node as _node  # queue / packer / ledger signatures
     _node.bind(lib)
     _lib = lib
@@ -370,6 +396,34 @@ class BatchVerifier:
         _check(self._lib.at2v_decode_points(self._h, _ptr(pts), n, _ptr(words)), "at2v_decode_points")
         return unpack_verdicts(words, n)
 
+    def reject_reasons(self, pk: np.ndarray, sig: np.ndarray, verdict_words: np.ndarray) -> np.ndarray:
+        """host arrays and the verdict words of a verify call over them (uint32, ceil(n/32); or bool[n] verdicts) ->
+        u8[n] at2v_reason per record: 0 where the verdict bit is set, else the first failing check (REASON_*). The pass
+        does not re-verify. A failed call raises; the library has then filled every byte with REASON_UNKNOWN."""
+        pk = np.ascontiguousarray(pk, dtype=np.uint8)
+        sig = np.ascontiguousarray(sig, dtype=np.uint8)
+        n = pk.size // 32
+        w = np.asarray(verdict_words)
+        if w.dtype == bool:
+            if w.shape != (n,):
+                raise ValueError("bool verdicts must have one entry per record")
+            b = np.packbits(w.astype(np.uint8), bitorder="little")
+            w = np.concatenate([b, np.zeros((-len(b)) % 4, np.uint8)]).view("<u4")
+        words = np.ascontiguousarray(w, dtype=np.uint32).reshape(-1)
+        if pk.size != 32 * n or sig.size != 64 * n or words.size < (n + 31) // 32:
+            raise ValueError("pk/sig/verdict_words sizes disagree")
+        reasons = np.full(max(1, n), REASON_UNKNOWN, np.uint8)
+        _check(self._lib.at2v_reject_reasons(self._h, _ptr(pk), _ptr(sig), n, _ptr(words), _ptr(reasons)),
+               "at2v_reject_reasons")
+        return reasons[:n]
+
+    def reject_reasons_device(self, d_pk: int, d_sig: int, n: int, d_verdicts: int, d_reasons: int,
+                              stream: int = 0) -> None:
+        """device pointers, asynchronous on `stream`: enqueue right after verify_batch_device on the same stream with
+        its d_pk, d_sig and d_verdicts; d_reasons receives n bytes (16-byte aligned)"""
+        _check(self._lib.at2v_reject_reasons_device(self._h, d_pk, d_sig, n, d_verdicts, d_reasons, stream or None),
+               "at2v_reject_reasons_device")
+
     def sign_batch(self, seeds: np.ndarray, msg: np.ndarray, msg_off: np.ndarray):
         seeds = np.ascontiguousarray(seeds, dtype=np.uint8)
         msg = np.ascontiguousarray(msg, dtype=np.uint8).reshape(-1)
@@ -397,6 +451,15 @@ def verify_one(pk: bytes, sig: bytes, msg: bytes, policy="dalek") -> bool:
         raise ValueError("public key must be 32 bytes and signature 64 bytes")
     return bool(_check(lib.at2v_verify_one_policy(bytes(pk), bytes(sig), bytes(msg) if msg else None, len(msg),
                                                   _POLICIES[policy]), "at2v_verify_one_policy"))
+
+
+def verify_one_reason(pk: bytes, sig: bytes, msg: bytes, policy="dalek") -> int:
+    """One signature on the CPU -> its at2v_reason (REASON_VALID = 0 for a valid one; at2v_verify_one_reason)."""
+    lib = load_library()
+    if len(pk) != 32 or len(sig) != 64:
+        raise ValueError("public key must be 32 bytes and signature 64 bytes")
+    return _check(lib.at2v_verify_one_reason(bytes(pk), bytes(sig), bytes(msg) if msg else None, len(msg),
+                                             _POLICIES[policy]), "at2v_verify_one_reason")
 
 
 # ------------------------------------------------ drop::crypto::sign mirror
@@ -432,5 +495,6 @@ class Signature:
     def verify(self, message: bytes, public_key: PublicKey) -> None:
         """Raise VerifyError unless the signature is valid (at2v_verify_one: the per-signature CPU entry point,
         as drop's synchronous verify is; batches go through BatchVerifier on the GPU)."""
-        if not verify_one(public_key.bytes, self.bytes, bytes(message)):
-            raise VerifyError("signature verification failed")
+        reason = verify_one_reason(public_key.bytes, self.bytes, bytes(message))
+        if reason != REASON_VALID:
+            raise VerifyError(f"signature verification failed: {reason_name(reason)}", reason)

@@ -68,6 +68,7 @@ QUEUE_EAGER = 1  # include/at2v.h AT2V_QUEUE_EAGER: also seal whenever no batch 
 QUEUE_SENDER_COMB = 2  # include/at2v.h AT2V_QUEUE_SENDER_COMB: per-sender combs in the queue's context
 QUEUE_CPU = 4  # include/at2v.h AT2V_QUEUE_CPU: batches verified by the CPU backend (no device)
 QUEUE_CPU_FALLBACK = 8  # include/at2v.h AT2V_QUEUE_CPU_FALLBACK: a batch that fails on the device re-runs on the CPU
+QUEUE_REASONS = 16  # include/at2v.h AT2V_QUEUE_REASONS: every batch also yields a reason byte per record (poll_reasons)
 
 
 class _QueueOpts(ctypes.Structure):
@@ -106,6 +107,7 @@ def bind(lib) -> None:
         "at2v_queue_submit": ([P, P, P, P, P, sz, ctypes.POINTER(u64)], i32),
         "at2v_queue_flush": ([P], i32),
         "at2v_queue_poll": ([P, P, P, sz, u32], ctypes.c_long),
+        "at2v_queue_poll_reasons": ([P, P, P, sz, u32], ctypes.c_long),
         "at2v_queue_get_stats": ([P, ctypes.POINTER(_QueueStats)], i32),
         "at2v_queue_reset_latency": ([P], i32),
         "at2v_pack_send_asset": ([P, sz, i32, P, P, P, P, P, P], ctypes.c_long),
@@ -145,14 +147,16 @@ class IngestQueue:
 
     def __init__(self, device: int = 0, policy="dalek", max_batch: int = 65536, max_delay_us: int = 1000,
                  max_msg_bytes: int = 256, depth: int = 3, eager: bool = False, sender_comb: bool = False,
-                 sender_cache: int = 0, cpu: bool = False, cpu_fallback: bool = False, cpu_threads: int = 0):
+                 sender_cache: int = 0, cpu: bool = False, cpu_fallback: bool = False, cpu_threads: int = 0,
+                 reasons: bool = False):
         """eager: also seal whenever no batch is in flight (latency mode); sender_comb: per-sender combs in the queue's
         context (at2v_comb.h) for `sender_cache` keys (0 = 1024; 1.7 MB of HBM per key); cpu: verify on the library's
-        CPU backend (no device); cpu_fallback: a batch that fails on the device is verified on the CPU backend instead"""
+        CPU backend (no device); cpu_fallback: a batch that fails on the device is verified on the CPU backend instead;
+        reasons: every batch also runs the reject-reasons pass, and poll_reasons returns an at2v_reason per ticket"""
         from . import _POLICIES
         self._lib = _lib()
         flags = ((QUEUE_EAGER if eager else 0) | (QUEUE_SENDER_COMB if sender_comb else 0) | (QUEUE_CPU if cpu else 0)
-                 | (QUEUE_CPU_FALLBACK if cpu_fallback else 0))
+                 | (QUEUE_CPU_FALLBACK if cpu_fallback else 0) | (QUEUE_REASONS if reasons else 0))
         o = _QueueOpts(device, _POLICIES[policy], max_batch, max_delay_us, max_msg_bytes, depth, flags, sender_cache,
                        cpu_threads)
         h = ctypes.c_void_p()
@@ -202,6 +206,15 @@ class IngestQueue:
         v = np.zeros(max_items, np.uint8)
         k = _chk(self._lib.at2v_queue_poll(self._h, _p(t), _p(v), max_items, timeout_us), "at2v_queue_poll")
         return t[:k], v[:k]
+
+    def poll_reasons(self, max_items: int = 65536, timeout_us: int = 0):
+        """-> (tickets u64[k], reasons u8[k]) in ticket order, as poll() with an at2v_reason per ticket: 0 valid, 1..6
+        why the record was rejected (at2v.REASON_*), 0xff its batch failed. Needs reasons=True (else At2vError -1)."""
+        t = np.zeros(max_items, np.uint64)
+        r = np.zeros(max_items, np.uint8)
+        k = _chk(self._lib.at2v_queue_poll_reasons(self._h, _p(t), _p(r), max_items, timeout_us),
+                 "at2v_queue_poll_reasons")
+        return t[:k], r[:k]
 
     def stats(self) -> dict:
         s = _QueueStats()

@@ -36,6 +36,7 @@
 #include "at2v_cpu.h"
 #include "at2v_env.h"
 #include "at2v_launch.h"
+#include "at2v_reason_launch.h"
 #include "at2v_shard.h"
 
 namespace {
@@ -168,6 +169,7 @@ struct Shard {
   DevBuf scratch[4];
   DevBuf part[4];  // per scratch set: the classify kernel's hit / miss lists (partitioned cached launches)
   DevBuf btab, pk, sig, msg, off, verdict;
+  DevBuf reasons;                // at2v_reject_reasons (host buffers): the gathered rejects' reason bytes
   hipEvent_t copied = nullptr;  // the verdict copy of a device-side call (decode, sharded)
   DevBuf hverdict[3];            // host-buffer calls: the shard's device bitmap per call slot (HostCall)
   hipEvent_t hcopied[3] = {nullptr, nullptr, nullptr};  // ... and its verdict copy (the call waits for this, not for
@@ -1054,6 +1056,7 @@ void at2v_destroy(at2v_ctx* ctx) {
     s.msg.release();
     s.off.release();
     s.verdict.release();
+    s.reasons.release();
     if (s.stream) (void)hipStreamDestroy(s.stream);
   }
   at2v::cpu_pool_destroy(ctx->cpu);
@@ -1566,6 +1569,111 @@ int at2v_decode_points(at2v_ctx* ctx, const uint8_t* pts, size_t n, uint32_t* va
   if (e == hipSuccess) e = hipStreamSynchronize(s.stream);
   (void)hipSetDevice(prev);
   return hip_code(e);
+}
+
+namespace {
+
+// The reject-reasons launch of a context (current device = the shard's). It takes no scratch set and records no event:
+// the pass reads only the caller's records and verdict words, so it orders nothing but its own stream.
+static hipError_t launch_reasons(at2v_ctx* ctx, const uint8_t* d_pk, const uint8_t* d_sig, size_t n,
+                                 const uint32_t* d_verdicts, uint8_t* d_reasons, hipStream_t stream) {
+  if (ctx->test_fail_launches) {  // test hook (AT2V_TEST_FAIL_LAUNCH): a launch failure, as a faulting device reports it
+    --ctx->test_fail_launches;
+    return hipErrorLaunchFailure;
+  }
+  if (!at2v::launch_reject_reasons) return hipErrorNoBinaryForGpu;  // linked without at2v_reason.o (a weak symbol)
+  return at2v::launch_reject_reasons(d_pk, d_sig, (uint32_t)n, d_verdicts, d_reasons, (int)ctx->policy, stream);
+}
+
+// The host form on a GPU context: only the m rejected records (idx, ascending) go to the device, with an all-zero
+// verdict array; their reason bytes come back into `got`.
+static hipError_t reasons_of_rejects(at2v_ctx* ctx, Shard& s, const uint8_t* pk, const uint8_t* sig,
+                                     const std::vector<uint32_t>& idx, std::vector<uint8_t>& got) {
+  const size_t m = idx.size(), words = (m + 31) / 32;
+  std::vector<uint8_t> gpk(m * 32), gsig(m * 64);
+  for (size_t k = 0; k < m; ++k) {
+    std::memcpy(&gpk[k * 32], pk + (size_t)idx[k] * 32, 32);
+    std::memcpy(&gsig[k * 64], sig + (size_t)idx[k] * 64, 64);
+  }
+  got.assign(m, AT2V_REASON_UNKNOWN);
+  hipError_t e = hipSetDevice(s.device);
+  if (e == hipSuccess) e = s.pk.ensure(m * 32);
+  if (e == hipSuccess) e = s.sig.ensure(m * 64);
+  if (e == hipSuccess) e = s.verdict.ensure(words * 4);
+  if (e == hipSuccess) e = s.reasons.ensure(m);
+  if (e == hipSuccess) e = hipMemcpyAsync(s.pk.p, gpk.data(), m * 32, hipMemcpyHostToDevice, s.stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(s.sig.p, gsig.data(), m * 64, hipMemcpyHostToDevice, s.stream);
+  if (e == hipSuccess) e = hipMemsetAsync(s.verdict.p, 0, words * 4, s.stream);
+  if (e == hipSuccess)
+    e = launch_reasons(ctx, (const uint8_t*)s.pk.p, (const uint8_t*)s.sig.p, m, (const uint32_t*)s.verdict.p,
+                       (uint8_t*)s.reasons.p, s.stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(got.data(), s.reasons.p, m, hipMemcpyDeviceToHost, s.stream);
+  // (also after an error: the pageable source arrays of the uploads die with this frame)
+  const hipError_t es = s.stream ? hipStreamSynchronize(s.stream) : hipSuccess;
+  return e != hipSuccess ? e : es;
+}
+
+}  // namespace
+
+int at2v_reject_reasons_device(at2v_ctx* ctx, const uint8_t* d_pk, const uint8_t* d_sig, size_t n,
+                               const uint32_t* d_verdicts, uint8_t* d_reasons, void* hip_stream) {
+  if (!ctx) return AT2V_E_INVALID;
+  if (n == 0) return AT2V_OK;
+  if (!d_pk || !d_sig || !d_verdicts || !d_reasons || n >= (1u << 31)) return AT2V_E_INVALID;
+  if (ctx->shards.empty()) return AT2V_E_NODEVICE;
+  if (!aligned(d_pk, 16) || !aligned(d_sig, 16) || !aligned(d_verdicts, 4) || !aligned(d_reasons, 16))
+    return AT2V_E_ALIGN;
+  Shard& s = ctx->shards[0];
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  hipError_t e = hipSetDevice(s.device);
+  if (e == hipSuccess) e = launch_reasons(ctx, d_pk, d_sig, n, d_verdicts, d_reasons, (hipStream_t)hip_stream);
+  (void)hipSetDevice(prev);
+  return hip_code(e);
+}
+
+int at2v_reject_reasons(at2v_ctx* ctx, const uint8_t* pk, const uint8_t* sig, size_t n, const uint32_t* verdicts,
+                        uint8_t* reasons) {
+  if (!ctx) return AT2V_E_INVALID;
+  if (n == 0) return AT2V_OK;
+  if (!reasons || n >= (1u << 31)) return AT2V_E_INVALID;
+  if (!pk || !sig || !verdicts) {
+    std::memset(reasons, AT2V_REASON_UNKNOWN, n);
+    return AT2V_E_INVALID;
+  }
+  if (ctx->shards.empty()) {  // CPU context: the same routine over its thread pool
+    at2v::cpu_reject_reasons(ctx->cpu, pk, sig, n, verdicts, (int)ctx->policy, reasons);
+    return AT2V_OK;
+  }
+  // valid records get their 0 here; only the rejected ones travel (a 1M batch with 10 % rejects uploads 10 MB, not 96)
+  std::vector<uint32_t> idx;
+  std::vector<uint8_t> got;
+  int rc = AT2V_OK;
+  try {
+    for (size_t w = 0; w < (n + 31) / 32; ++w) {
+      const size_t left = n - 32 * w;
+      uint32_t rej = ~verdicts[w] & (left >= 32 ? 0xffffffffu : (1u << left) - 1u);  // pad bits are not rejects
+      for (; rej; rej &= rej - 1) idx.push_back((uint32_t)(32 * w) + (uint32_t)__builtin_ctz(rej));
+    }
+    std::memset(reasons, AT2V_REASON_VALID, n);
+    if (idx.empty()) return AT2V_OK;
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    rc = hip_code(reasons_of_rejects(ctx, ctx->shards[0], pk, sig, idx, got));
+    (void)hipSetDevice(prev);
+  } catch (const std::bad_alloc&) {
+    rc = AT2V_E_OOM;
+  }
+  if (rc == AT2V_OK) {
+    for (size_t k = 0; k < idx.size(); ++k) reasons[idx[k]] = got[k];
+    return AT2V_OK;
+  }
+  if (ctx->cpu) {  // AT2V_CTX_CPU_FALLBACK: the records are still on the host
+    at2v::cpu_reject_reasons(ctx->cpu, pk, sig, n, verdicts, (int)ctx->policy, reasons);
+    return AT2V_OK;
+  }
+  std::memset(reasons, AT2V_REASON_UNKNOWN, n);  // fail closed
+  return rc;
 }
 
 int at2v_get_info(at2v_ctx* ctx, at2v_info* out) {

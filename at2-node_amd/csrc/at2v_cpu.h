@@ -35,6 +35,11 @@ void cpu_verify_batch(CpuPool* p, const uint8_t* pk, const uint8_t* sig, const u
 // bit i of valid_words = 1 iff pts[i] decodes under dalek rules (the kernels' gu_frombytes), synchronous
 void cpu_decode_points(CpuPool* p, const uint8_t* pts, size_t n, uint32_t* valid_words);
 
+// reasons[i] = the at2v_reason of record i (at2v_reason.h reject_reason; 0 where bit i of verdict_words is set), n bytes,
+// synchronous. policy: AT2V_POLICY_*. Chunks of 64 records own their bytes.
+void cpu_reject_reasons(CpuPool* p, const uint8_t* pk, const uint8_t* sig, size_t n, const uint32_t* verdict_words,
+                        int policy, uint8_t* reasons);
+
 // One record through the joint-table form of the verify routine (verify_half_fu_joint, what the GPU's verify_kernel
 // runs) with the host tables: the verdict at2v_verify_one_policy gives, 0 or 1. For tests (tests/host/joint_host.cpp);
 // not part of the ABI. Arguments as at2v_verify_one_policy's, already checked.

@@ -29,6 +29,7 @@ struct DevSlot {
   uint8_t* host = nullptr; // pinned host allocation (slot.pk points at its start)
   size_t msg_at = 0;       // byte offset of msg in both allocations
   void *pk = nullptr, *sig = nullptr, *msg = nullptr, *off = nullptr, *ver = nullptr;
+  void* reasons = nullptr;  // AT2V_QUEUE_REASONS without direct writes: the batch's reason bytes on the device
   hipEvent_t uploaded = nullptr, verified = nullptr, done = nullptr;
   hipStream_t stream = nullptr;  // the compute stream of the slot's last launch
   bool cpu_done = false;         // the slot's batch was verified on the CPU backend (AT2V_QUEUE_CPU[_FALLBACK])
@@ -83,8 +84,13 @@ struct HipBackend {
   // process (0.54-0.56 ms); priority changed nothing (profiles/r05f).
   int ncomp = 2;
   bool prio = false;
+  // AT2V_QUEUE_REASONS: every batch's launch is followed, on the same stream, by the reject-reasons pass over its
+  // records and verdict words; the bytes land in the slot's pinned reason bytes (written there by the kernel when the
+  // verdict words are, else downloaded with them). CPU and fallback batches run the CPU routine.
+  bool reasons = false;
 
   int init(const at2v_queue_opts& o) {
+    reasons = (o.flags & AT2V_QUEUE_REASONS) != 0;
     at2v_opts co{o.device, 1, o.policy, 0, 0, 0, o.cpu_threads, 0};
     if (o.flags & AT2V_QUEUE_CPU) {
       cpu_only = true;
@@ -152,7 +158,8 @@ struct HipBackend {
     if (cpu_only) {  // host memory only
       d->host = static_cast<uint8_t*>(std::malloc(bytes));
       s.verdicts = static_cast<uint32_t*>(std::malloc(words * 4));
-      if (!d->host || !s.verdicts) return AT2V_E_OOM;
+      if (reasons) s.reasons = static_cast<uint8_t*>(std::malloc(cap));
+      if (!d->host || !s.verdicts || (reasons && !s.reasons)) return AT2V_E_OOM;
       s.pk = d->host;
       s.sig = d->host + cap * 32;
       s.off = reinterpret_cast<uint32_t*>(d->host + cap * 96);
@@ -164,6 +171,9 @@ struct HipBackend {
     bool ok = hipHostMalloc((void**)&d->host, bytes, hipHostMallocDefault) == hipSuccess &&
               hipHostMalloc((void**)&s.verdicts, words * 4, hipHostMallocDefault) == hipSuccess &&
               hipMalloc((void**)&d->dev, bytes) == hipSuccess && hipMalloc(&d->ver, words * 4) == hipSuccess;
+    if (ok && reasons)
+      ok = hipHostMalloc((void**)&s.reasons, cap, hipHostMallocDefault) == hipSuccess &&
+           hipMalloc(&d->reasons, cap) == hipSuccess;
     if (ok) {
       s.pk = d->host;
       s.sig = d->host + cap * 32;
@@ -182,6 +192,8 @@ struct HipBackend {
   void release(at2v::QueueSlot& s) {
     if (cpu_only) {
       std::free(s.verdicts);
+      std::free(s.reasons);
+      s.reasons = nullptr;
       DevSlot* d = static_cast<DevSlot*>(s.backend);
       if (d) std::free(d->host);
       delete d;
@@ -192,12 +204,14 @@ struct HipBackend {
     }
     const DeviceScope scope(device);
     if (s.verdicts) (void)hipHostFree(s.verdicts);
+    if (s.reasons) (void)hipHostFree(s.reasons);
+    s.reasons = nullptr;
     s.pk = s.sig = s.msg = nullptr;
     s.off = s.verdicts = nullptr;
     DevSlot* d = static_cast<DevSlot*>(s.backend);
     if (!d) return;
     if (d->host) (void)hipHostFree(d->host);
-    for (void* p : {(void*)d->dev, d->ver})
+    for (void* p : {(void*)d->dev, d->ver, d->reasons})
       if (p) (void)hipFree(p);
     for (hipEvent_t e : {d->uploaded, d->verified, d->done})
       if (e) (void)hipEventDestroy(e);
@@ -208,7 +222,18 @@ struct HipBackend {
   // copy on the same comp stream with AT2V_QUEUE_DIRECT=0)
   // the slot's records on the CPU backend (cpu_ctx for a fallback), verdicts into its host words
   int verify_on_cpu(at2v::QueueSlot& s, at2v_ctx* c) {
-    return at2v_verify_batch(c, s.pk, s.sig, s.msg, s.off, s.n, s.verdicts);
+    const int rc = at2v_verify_batch(c, s.pk, s.sig, s.msg, s.off, s.n, s.verdicts);
+    if (rc != AT2V_OK || !reasons) return rc;
+    return at2v_reject_reasons(c, s.pk, s.sig, s.n, s.verdicts, s.reasons);  // (a CPU context: cpu_reject_reasons)
+  }
+  // the reasons pass of a batch just launched on `comp`: the same records and the words its verify writes
+  int launch_reasons(at2v::QueueSlot& s, DevSlot* d, const void* pk, const void* sig, const uint32_t* ver,
+                     hipStream_t comp) {
+    if (!reasons) return AT2V_OK;
+    uint8_t* out = direct ? s.reasons : (uint8_t*)d->reasons;
+    const int rc = at2v_reject_reasons_device(ctx, (const uint8_t*)pk, (const uint8_t*)sig, s.n, ver, out, comp);
+    if (rc || direct) return rc;
+    return hipMemcpyAsync(s.reasons, d->reasons, s.n, hipMemcpyDeviceToHost, comp) == hipSuccess ? AT2V_OK : AT2V_E_HIP;
   }
   // a batch the device failed: drain what the slot's stream may still write into its verdict words, then the CPU
   int fall_back(at2v::QueueSlot& s, int rc) {
@@ -239,7 +264,8 @@ struct HipBackend {
     if (n <= zerocopy_max) {  // the kernel reads the pinned host buffers (same layout) directly
       uint32_t* ver = direct ? s.verdicts : (uint32_t*)d->ver;
       if (e != hipSuccess) return AT2V_E_HIP;
-      const int rc = at2v_verify_batch_device(ctx, s.pk, s.sig, s.msg, s.msg_used, s.off, n, ver, comp);
+      int rc = at2v_verify_batch_device(ctx, s.pk, s.sig, s.msg, s.msg_used, s.off, n, ver, comp);
+      if (rc == AT2V_OK) rc = launch_reasons(s, d, s.pk, s.sig, ver, comp);
       if (rc) return rc;
       if (!direct) e = hipMemcpyAsync(s.verdicts, d->ver, words * 4, hipMemcpyDeviceToHost, comp);
       if (e == hipSuccess) e = hipEventRecord(d->done, comp);
@@ -258,8 +284,9 @@ struct HipBackend {
     if (e == hipSuccess) e = hipStreamWaitEvent(comp, d->uploaded, 0);
     if (e != hipSuccess) return AT2V_E_HIP;
     uint32_t* ver = direct ? s.verdicts : (uint32_t*)d->ver;
-    const int rc = at2v_verify_batch_device(ctx, (const uint8_t*)d->pk, (const uint8_t*)d->sig, (const uint8_t*)d->msg,
-                                            s.msg_used, (const uint32_t*)d->off, n, ver, comp);
+    int rc = at2v_verify_batch_device(ctx, (const uint8_t*)d->pk, (const uint8_t*)d->sig, (const uint8_t*)d->msg,
+                                      s.msg_used, (const uint32_t*)d->off, n, ver, comp);
+    if (rc == AT2V_OK) rc = launch_reasons(s, d, d->pk, d->sig, ver, comp);
     if (rc) return rc;
     if (!direct) e = hipMemcpyAsync(s.verdicts, d->ver, words * 4, hipMemcpyDeviceToHost, comp);
     if (e == hipSuccess) e = hipEventRecord(d->done, comp);
@@ -314,8 +341,10 @@ int at2v_queue_create(const at2v_queue_opts* opts, at2v_queue** out) {
   if (o.max_msg_bytes) qo.max_msg_bytes = o.max_msg_bytes;
   if (o.depth) qo.depth = (int)o.depth;
   qo.eager = (o.flags & AT2V_QUEUE_EAGER) != 0;
+  qo.reasons = (o.flags & AT2V_QUEUE_REASONS) != 0;
   if (const char* v = at2v::test_env("AT2V_QUEUE_LAUNCH_HERE")) qo.launch_here = std::atoi(v) != 0;  // (A/B)
-  if (o.flags & ~(AT2V_QUEUE_EAGER | AT2V_QUEUE_SENDER_COMB | AT2V_QUEUE_CPU | AT2V_QUEUE_CPU_FALLBACK))
+  if (o.flags &
+      ~(AT2V_QUEUE_EAGER | AT2V_QUEUE_SENDER_COMB | AT2V_QUEUE_CPU | AT2V_QUEUE_CPU_FALLBACK | AT2V_QUEUE_REASONS))
     return AT2V_E_INVALID;
   if ((o.flags & AT2V_QUEUE_CPU) && (o.flags & (AT2V_QUEUE_SENDER_COMB | AT2V_QUEUE_CPU_FALLBACK))) return AT2V_E_INVALID;
   if (qo.depth < 2 || qo.max_batch >= (1u << 31) || (uint64_t)qo.max_batch * qo.max_msg_bytes >= (1ull << 32))
@@ -359,6 +388,12 @@ int at2v_queue_flush(at2v_queue* q) {
 long at2v_queue_poll(at2v_queue* q, uint64_t* tickets, uint8_t* verdicts, size_t max, uint32_t timeout_us) {
   if (!q || !q->q || (max && (!tickets || !verdicts))) return AT2V_E_INVALID;
   return q->q->poll(tickets, verdicts, max, timeout_us);
+}
+
+long at2v_queue_poll_reasons(at2v_queue* q, uint64_t* tickets, uint8_t* reasons, size_t max, uint32_t timeout_us) {
+  if (!q || !q->q || (max && (!tickets || !reasons))) return AT2V_E_INVALID;
+  const long k = q->q->poll_reasons(tickets, reasons, max, timeout_us);
+  return k < 0 ? AT2V_E_INVALID : k;
 }
 
 int at2v_queue_get_stats(at2v_queue* q, at2v_queue_stats* out) {

@@ -41,6 +41,7 @@ struct QueueOpts {
   int depth = 3;               // slots: 1 filling + up to depth-1 in flight
   bool eager = false;          // also seal whenever the device is idle (no batch in flight)
   bool launch_here = true;     // eager: the producer / completer that finds the device idle launches the batch itself
+  bool reasons = false;        // every batch also yields a reason byte per record (QueueSlot::reasons, poll_reasons)
 };
 
 struct QueueSlot {
@@ -50,6 +51,7 @@ struct QueueSlot {
   uint8_t* msg = nullptr;
   uint32_t* off = nullptr;
   uint32_t* verdicts = nullptr;
+  uint8_t* reasons = nullptr;  // QueueOpts::reasons: cap_records bytes the backend fills for the batch's n records
   size_t cap_records = 0, cap_msg = 0;
   size_t n = 0, msg_used = 0;
   uint64_t first_ticket = 0;
@@ -201,6 +203,27 @@ class BatchQueue {
     return (long)k;
   }
 
+  // The same with a reason byte per ticket (0 valid, 1..6 why the record was rejected, 0xff its batch failed);
+  // -1 unless the queue was created with QueueOpts::reasons.
+  long poll_reasons(uint64_t* tickets, uint8_t* reasons, size_t max, uint32_t timeout_us) {
+    if (!o_.reasons) return -1;
+    std::unique_lock<std::mutex> lk(m_);
+    if (done_.empty() && timeout_us)
+      cv_done_.wait_for(lk, std::chrono::microseconds(timeout_us), [&] { return !done_.empty(); });
+    size_t k = 0;
+    while (k < max && !done_.empty()) {
+      Done& d = done_.front();
+      while (k < max && d.used < d.n) {
+        const size_t i = d.used++;
+        tickets[k] = d.first + i;
+        reasons[k] = d.failed ? 0xff : d.reasons[i];
+        ++k;
+      }
+      if (d.used == d.n) done_.pop_front();
+    }
+    return (long)k;
+  }
+
   QueueStats stats() {
     std::lock_guard<std::mutex> lk(m_);
     QueueStats s = stats_;
@@ -230,6 +253,7 @@ class BatchQueue {
     size_t n, used;
     bool failed;
     std::vector<uint32_t> words;
+    std::vector<uint8_t> reasons;  // QueueOpts::reasons
   };
 
   // every slot that start() touched, including a partly allocated one (release() skips null buffers)
@@ -308,8 +332,10 @@ class BatchQueue {
       const uint64_t t = now_us();
       lk.lock();
       inflight_.pop_front();
-      Done d{s->first_ticket, s->n, 0, st != 0, {}};
+      Done d{s->first_ticket, s->n, 0, st != 0, {}, {}};
       d.words.assign(s->verdicts, s->verdicts + (s->n + 31) / 32);
+      if (o_.reasons && s->reasons && st == 0) d.reasons.assign(s->reasons, s->reasons + s->n);
+      if (o_.reasons && d.reasons.size() != s->n) d.failed = true;  // (no bytes: never a reason read out of bounds)
       done_.push_back(std::move(d));
       for (const auto& r : s->t_runs) {
         const uint32_t d = (uint32_t)std::min<uint64_t>(t - r.second, UINT32_MAX);

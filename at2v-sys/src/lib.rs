@@ -31,7 +31,7 @@ pub struct At2vLedger {
 
 /// include/at2v.h AT2V_ABI_VERSION: the layouts of the #[repr(C)] structs below. `BatchVerifier::new` and
 /// `Queue::new` refuse a library that reports another version (the structs are copied whole by the library).
-pub const AT2V_ABI_VERSION: c_int = 7;
+pub const AT2V_ABI_VERSION: c_int = 8;
 
 pub const AT2V_POLICY_DALEK_V1: c_int = 0;
 pub const AT2V_POLICY_LIBSODIUM_1_0_18: c_int = 1;
@@ -66,6 +66,48 @@ pub const AT2V_TX_FAILURE: i32 = 2;
 pub const AT2V_VERDICT_INVALID: u8 = 0;
 pub const AT2V_VERDICT_VALID: u8 = 1;
 pub const AT2V_VERDICT_FAILED: u8 = 0xff;
+
+/// include/at2v.h at2v_reason: the bytes of at2v_reject_reasons / at2v_queue_poll_reasons
+pub const AT2V_REASON_VALID: u8 = 0;
+pub const AT2V_REASON_A_DECODE: u8 = 1;
+pub const AT2V_REASON_S_RANGE: u8 = 2;
+pub const AT2V_REASON_A_POLICY: u8 = 3;
+pub const AT2V_REASON_R_POLICY: u8 = 4;
+pub const AT2V_REASON_R_ENCODING: u8 = 5;
+pub const AT2V_REASON_EQUATION: u8 = 6;
+pub const AT2V_REASON_UNKNOWN: u8 = 255;
+
+/// Why a record was rejected (at2v_reason, the header's values). `ADecode` is what the reference answers with
+/// InvalidArgument at ingest (rpc.rs:240-243, :265-269); `SRange`..`Equation` are a payload that is never delivered.
+#[repr(u8)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum RejectReason {
+    Valid = 0,
+    ADecode = 1,
+    SRange = 2,
+    APolicy = 3,
+    RPolicy = 4,
+    REncoding = 5,
+    Equation = 6,
+    /// the call or the batch failed: neither valid nor invalid
+    Unknown = 255,
+}
+
+impl RejectReason {
+    /// Any byte that is not a reason of the header reads as `Unknown` (fail closed).
+    pub fn from_byte(b: u8) -> RejectReason {
+        match b {
+            AT2V_REASON_VALID => RejectReason::Valid,
+            AT2V_REASON_A_DECODE => RejectReason::ADecode,
+            AT2V_REASON_S_RANGE => RejectReason::SRange,
+            AT2V_REASON_A_POLICY => RejectReason::APolicy,
+            AT2V_REASON_R_POLICY => RejectReason::RPolicy,
+            AT2V_REASON_R_ENCODING => RejectReason::REncoding,
+            AT2V_REASON_EQUATION => RejectReason::Equation,
+            _ => RejectReason::Unknown,
+        }
+    }
+}
 
 /// `Default`: device 0, one GPU, DALEK_V1, library-default small-batch threshold, no sender cache, no CPU fallback.
 /// (Not derived: `num_gpus = 0` selects the CPU batch backend since ABI version 6.)
@@ -170,6 +212,8 @@ pub const AT2V_QUEUE_SENDER_COMB: u32 = 2;
 pub const AT2V_QUEUE_CPU: u32 = 4;
 /// `At2vQueueOpts::flags`: a batch the device fails is verified on the CPU backend instead.
 pub const AT2V_QUEUE_CPU_FALLBACK: u32 = 8;
+/// `At2vQueueOpts::flags`: every batch also runs the reject-reasons pass; `Queue::poll_reasons` reads the bytes.
+pub const AT2V_QUEUE_REASONS: u32 = 16;
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -237,6 +281,12 @@ extern "C" {
     pub fn at2v_verify_one(pk: *const u8, sig: *const u8, msg: *const u8, len: usize) -> c_int;
     pub fn at2v_verify_one_policy(pk: *const u8, sig: *const u8, msg: *const u8, len: usize, policy: c_int) -> c_int;
     pub fn at2v_strerror(code: c_int) -> *const c_char;
+    pub fn at2v_reject_reasons_device(ctx: *mut At2vCtx, d_pk: *const u8, d_sig: *const u8, n: usize,
+                                      d_verdicts: *const u32, d_reasons: *mut u8, hip_stream: *mut c_void) -> c_int;
+    pub fn at2v_reject_reasons(ctx: *mut At2vCtx, pk: *const u8, sig: *const u8, n: usize, verdicts: *const u32,
+                               reasons: *mut u8) -> c_int;
+    pub fn at2v_verify_one_reason(pk: *const u8, sig: *const u8, msg: *const u8, len: usize, policy: c_int) -> c_int;
+    pub fn at2v_reason_name(reason: c_int) -> *const c_char;
     pub fn at2v_gen_records_device(ctx: *mut At2vCtx, cfg_seed: u64, first: u64, n: usize, msg_len: u32,
                                    d_pk: *mut u8, d_sig: *mut u8, d_msg: *mut u8, d_msg_off: *mut u32,
                                    hip_stream: *mut c_void) -> c_int;
@@ -266,6 +316,8 @@ extern "C" {
     pub fn at2v_queue_flush(q: *mut At2vQueue) -> c_int;
     pub fn at2v_queue_poll(q: *mut At2vQueue, tickets: *mut u64, verdicts: *mut u8, max: usize, timeout_us: u32)
                            -> c_long;
+    pub fn at2v_queue_poll_reasons(q: *mut At2vQueue, tickets: *mut u64, reasons: *mut u8, max: usize, timeout_us: u32)
+                                   -> c_long;
     pub fn at2v_queue_get_stats(q: *mut At2vQueue, out: *mut At2vQueueStats) -> c_int;
     pub fn at2v_queue_reset_latency(q: *mut At2vQueue) -> c_int;
 
@@ -404,6 +456,22 @@ impl BatchVerifier {
             .map(|_| ())
     }
 
+    /// Why each record of a verified batch was rejected: `pk` / `sig` as given to `verify`, `verdicts` as it returned
+    /// them. `Valid` where the verdict is true, else the first failing check. The pass does not re-verify.
+    pub fn reject_reasons(&mut self, pk: &[u8], sig: &[u8], verdicts: &[bool]) -> Result<Vec<RejectReason>, Error> {
+        let n = verdicts.len();
+        if pk.len() != 32 * n || sig.len() != 64 * n {
+            return Err(Error(AT2V_E_INVALID));
+        }
+        let mut words = vec![0u32; (n + 31) / 32];
+        for (i, &v) in verdicts.iter().enumerate() {
+            words[i / 32] |= (v as u32) << (i % 32);
+        }
+        let mut bytes = vec![AT2V_REASON_UNKNOWN; n];
+        check(unsafe { at2v_reject_reasons(self.0, pk.as_ptr(), sig.as_ptr(), n, words.as_ptr(), bytes.as_mut_ptr()) })?;
+        Ok(bytes.into_iter().map(RejectReason::from_byte).collect())
+    }
+
     pub fn info(&self) -> Result<At2vInfo, Error> {
         let mut i = At2vInfo::default();
         check(unsafe { at2v_get_info(self.0, &mut i) })?;
@@ -461,6 +529,18 @@ impl Queue {
         Ok((0..k as usize)
             .map(|i| (t[i], match v[i] { AT2V_VERDICT_VALID => Some(true), AT2V_VERDICT_INVALID => Some(false), _ => None }))
             .collect())
+    }
+
+    /// As `poll`, with the reason of every ticket (`Unknown`: its batch failed). The queue must have been created with
+    /// AT2V_QUEUE_REASONS (Err(AT2V_E_INVALID) otherwise).
+    pub fn poll_reasons(&self, max: usize, timeout_us: u32) -> Result<Vec<(u64, RejectReason)>, Error> {
+        let mut t = vec![0u64; max];
+        let mut r = vec![AT2V_REASON_UNKNOWN; max];
+        let k = unsafe { at2v_queue_poll_reasons(self.0, t.as_mut_ptr(), r.as_mut_ptr(), max, timeout_us) };
+        if k < 0 {
+            return Err(Error(k as c_int));
+        }
+        Ok((0..k as usize).map(|i| (t[i], RejectReason::from_byte(r[i]))).collect())
     }
 
     pub fn stats(&self) -> Result<At2vQueueStats, Error> {

@@ -26,6 +26,8 @@ extern "C" {
 #endif
 
 /* ABI version of this header. Every struct passed by pointer is copied whole, so adding a field is an ABI break:
+ * version 8 added the reject reasons (at2v_reject_reasons / _device, at2v_verify_one_reason, at2v_reason_name,
+ * at2v_queue_poll_reasons with the AT2V_QUEUE_REASONS queue flag; no struct changed);
  * version 7 appended at2v_info.experiments / host_chunks (and the AT2V_EXPERIMENT_* bits) and added
  * at2v_verify_batch_submit / _wait; version 6 appended at2v_opts.cpu_threads / flags (num_gpus = 0 now means the CPU batch backend, no device),
  * at2v_info.cpu_threads / cpu_batches / cpu_fallbacks / cache_sightings / cache_built / cache_build_us /
@@ -36,7 +38,7 @@ extern "C" {
  * at2v_opts.sender_comb and the AT2V_QUEUE_SENDER_COMB queue flag; version 3 appended at2v_opts.sender_cache, at2v_info.gathers / cache_* and the AT2V_E_PEER code (version 2 appended
  * at2v_opts.small_batch_max and at2v_queue_opts.flags). A binding checks at2v_abi_version() == AT2V_ABI_VERSION
  * before passing any struct (the Python and Rust bindings in this repo refuse a mismatching library). */
-#define AT2V_ABI_VERSION 7
+#define AT2V_ABI_VERSION 8
 int at2v_abi_version(void);
 
 typedef struct at2v_ctx at2v_ctx; /* opaque: device(s), streams, scratch, staging buffers, and the RCCL
@@ -127,7 +129,8 @@ void at2v_destroy(at2v_ctx* ctx);
  *   msg      concatenated messages; message i = msg[msg_off[i] .. msg_off[i+1]) (M = bincode(ThinTransaction))
  *   msg_off  n + 1 offsets, non-decreasing, msg_off[0] may be > 0
  *   verdicts ceil(n/32) words out; bit (i % 32) of word (i / 32) = 1 iff record i is valid. Pad bits are 0.
- * Malformed records (undecodable A, s >= l, wrong equation, ...) are verdict 0, never an error.
+ * Malformed records (undecodable A, s >= l, wrong equation, ...) are verdict 0, never an error; which of those
+ * causes it was is answered afterwards by at2v_reject_reasons (below).
  * The library does not retain any pointer after return. n may be 0. n < 2^31. */
 int at2v_verify_batch(at2v_ctx* ctx, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg,
                       const uint32_t* msg_off, size_t n, uint32_t* verdicts);
@@ -171,6 +174,46 @@ int at2v_verify_one(const uint8_t pk[32], const uint8_t sig[64], const uint8_t* 
 int at2v_verify_one_policy(const uint8_t pk[32], const uint8_t sig[64], const uint8_t* msg, size_t len, int policy);
 
 const char* at2v_strerror(int code);
+
+/* ---- why a record was rejected (a second, cheap pass over the records whose verdict bit is 0) ----
+ * The reference tells these causes apart: an undecodable sender key is answered with InvalidArgument at ingest
+ * (rpc.rs:240-243, :265-269), and dalek separates a signature that does not parse (s >= l) from one that fails the
+ * equation. A record whose verdict bit is set is VALID; any other record gets the LOWEST-numbered failing check, tested
+ * in the order of the enum: the key first (as the reference decodes it at ingest), then the signature's scalar (as
+ * Signature::from_bytes does), then the policy pre-rejects, then R, then the equation. Under AT2V_POLICY_DALEK_V1
+ * reasons 3 and 4 never occur. The reason is a function of (A, R, S, policy) and the verdict bit alone; the message is
+ * not needed: if every cheap check passes and the bit is 0, the cause is the equation, by elimination. The pass does
+ * NOT re-verify: a caller who hands in a 0 bit for a record that is in fact valid gets AT2V_REASON_EQUATION. */
+typedef enum {
+  AT2V_REASON_VALID = 0,      /* verdict bit 1 */
+  AT2V_REASON_A_DECODE = 1,   /* V2: A is not a curve point (dalek decompress fails): rpc.rs:269 InvalidArgument */
+  AT2V_REASON_S_RANGE = 2,    /* V1: s >= l */
+  AT2V_REASON_A_POLICY = 3,   /* LIBSODIUM policy only: A's y non-canonical, or A on the small-order blocklist */
+  AT2V_REASON_R_POLICY = 4,   /* LIBSODIUM policy only: R on the small-order blocklist */
+  AT2V_REASON_R_ENCODING = 5, /* R is not the canonical encoding of a curve point (y >= p, x = 0 with the sign bit, or
+                                 not on the curve): no R' can compare equal to these bytes */
+  AT2V_REASON_EQUATION = 6,   /* everything well-formed; enc([s]B - [k]A) != R */
+  AT2V_REASON_UNKNOWN = 255   /* 0xff: the call or the batch failed; neither valid nor invalid */
+} at2v_reason;
+
+/* Device buffers of ctx's first device (AT2V_E_NODEVICE on a CPU context), asynchronous on `hip_stream`: meant to be
+ * enqueued right after at2v_verify_batch_device or at2v_verify_shard_gather_device on the same stream, with the pk and
+ * sig of that call and the verdict words it writes. d_reasons receives n bytes (an at2v_reason each; bytes of valid
+ * records are written too, as 0; nothing is written at or after d_reasons + n). d_pk / d_sig / d_reasons 16-byte
+ * aligned, d_verdicts 4-byte aligned (AT2V_E_ALIGN). Uses none of the context's scratch sets and never touches the
+ * sender cache: it adds no ordering between verify launches. */
+int at2v_reject_reasons_device(at2v_ctx* ctx, const uint8_t* d_pk, const uint8_t* d_sig, size_t n,
+                               const uint32_t* d_verdicts, uint8_t* d_reasons, void* hip_stream);
+/* Host buffers, synchronous, any context. verdicts: the ceil(n/32) words of a verify call over the same records;
+ * reasons: n bytes out. A GPU context uploads only the rejected records (first device, its stream); a CPU context runs
+ * the same routine on its thread pool. On any error every one of the n bytes is AT2V_REASON_UNKNOWN (fail closed); with
+ * AT2V_CTX_CPU_FALLBACK a device error falls back to the CPU pool and the call returns AT2V_OK. n may be 0. */
+int at2v_reject_reasons(at2v_ctx* ctx, const uint8_t* pk, const uint8_t* sig, size_t n, const uint32_t* verdicts,
+                        uint8_t* reasons);
+/* One signature on the CPU: at2v_verify_one_policy, then the reason if the verdict is 0. Returns an at2v_reason (0..6)
+ * or a negative error code. */
+int at2v_verify_one_reason(const uint8_t pk[32], const uint8_t sig[64], const uint8_t* msg, size_t len, int policy);
+const char* at2v_reason_name(int reason);
 
 /* ---- signing side (client, src/client.rs:77-78), used to synthesise inputs on the GPU ---- */
 
@@ -285,7 +328,7 @@ typedef struct {
   uint32_t max_msg_bytes; /* message bytes budgeted per record (slot capacity max_batch x this); 0 = 256 */
   uint32_t depth;         /* batch slots, >= 2; 0 = 3 */
   uint32_t flags;         /* AT2V_QUEUE_EAGER: also seal whenever no batch is in flight; AT2V_QUEUE_SENDER_COMB:
-                             per-sender combs (at2v_opts.sender_comb) */
+                             per-sender combs (at2v_opts.sender_comb); AT2V_QUEUE_REASONS: at2v_queue_poll_reasons */
   uint32_t sender_cache;  /* with AT2V_QUEUE_SENDER_COMB: keys the queue's context caches (at2v_opts.sender_cache,
                              1.7 MB of HBM each); 0 = 1024 */
   uint32_t cpu_threads;   /* AT2V_QUEUE_CPU / AT2V_QUEUE_CPU_FALLBACK: host threads (0 = every usable CPU) */
@@ -295,6 +338,9 @@ typedef struct {
 #define AT2V_QUEUE_CPU 4u         /* batches verified by the CPU backend (a context with num_gpus = 0): no device */
 #define AT2V_QUEUE_CPU_FALLBACK 8u /* a batch whose launch or completion fails on the device is verified on the CPU
                                      backend instead (the slot's records are in host memory); same verdicts */
+#define AT2V_QUEUE_REASONS 16u     /* every batch also runs the reject-reasons pass (at2v_reject_reasons_device right
+                                     after its verify, same stream; the CPU routine on a CPU or fallback batch) and
+                                     at2v_queue_poll_reasons returns a reason byte per ticket */
 typedef struct {
   uint64_t submitted, completed, batches, failed_batches;
   double mean_batch;           /* records per completed batch */
@@ -311,6 +357,9 @@ int at2v_queue_flush(at2v_queue* q);
 /* Up to max completed (ticket, verdict) pairs in ticket order, waiting up to timeout_us for the first.
  * verdict: 1 valid, 0 invalid, 0xff the batch failed on the device. Returns the count (>= 0) or < 0. */
 long at2v_queue_poll(at2v_queue* q, uint64_t* tickets, uint8_t* verdicts, size_t max, uint32_t timeout_us);
+/* The same, with an at2v_reason byte per ticket instead of the verdict (0 = valid, 1..6 = why it was rejected, 0xff =
+ * the batch failed). A queue created without AT2V_QUEUE_REASONS returns AT2V_E_INVALID. */
+long at2v_queue_poll_reasons(at2v_queue* q, uint64_t* tickets, uint8_t* reasons, size_t max, uint32_t timeout_us);
 int at2v_queue_get_stats(at2v_queue* q, at2v_queue_stats* out);
 int at2v_queue_reset_latency(at2v_queue* q);
 
