@@ -2,7 +2,9 @@
 // add/sub with the multiple-of-p constants, carries, (de)serialisation, exponentiation chains (one and two at a
 // time) and predicates. Input/output classes of every function are the ones tools/gen_fu.py proves:
 //   carried : limb i < 2^W[i] (limb 1 <= 2^25 - 1 + kFuLimb1Spill) — output of every product, fu_carry, fu_frombytes
-//   fu_mul f: <= 4 carried units on even limbs, 4.5 on odd ones (limb 9: 6); fu_mul g, fu_sq: <= 3 on even limbs
+//   fu_mul f: <= 4 carried units on even limbs, 4.5 on odd ones (limb 9: 6); fu_mul g: <= 3 on even limbs
+//   fu_sq, fu_sq_x2: a sum of two carried elements; fu_sq2, fu_sqc, fu_sqc_x2: carried (the classes of their sites in
+//   at2v_gu.h, which decide their scaled-operand sets: at2v_fu_gen.h's header comment)
 #pragma once
 #include "at2v_fu_gen.h"
 

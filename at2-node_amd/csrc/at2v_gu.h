@@ -75,6 +75,8 @@ AT2V_HD AT2V_INLINE void gu_p1p1_to_p3(gu_p3& r, const gu_p1p1& p) {
 // dbl-2008-hwcd, p2 -> p1p1: XX = X^2, YY = Y^2, ZZ2 = 2 Z^2, t0 = (X+Y)^2;
 //   X' = XX + YY - t0 (= -2XY), Z' = XX - YY, Y' = XX + YY, T' = ZZ2 + XX - YY (even limbs carried into odd ones)
 //   x3 = X'/Z' = 2XY/(Y^2 - X^2), y3 = Y'/T' = (X^2 + Y^2)/(2Z^2 - Y^2 + X^2)
+// X, Y, Z carried (products, decoded points, the identity): the class of fu_sqc and fu_sq2, whose scaled operands
+// (38 f_j, 76 f_j) do not fit a wider one; every caller passes the output of gu_p1p1_to_p2 / _p3 or a decoded point.
 AT2V_HD AT2V_INLINE void gu_p2_dbl(gu_p1p1& r, const gu_p2& p) {
   fu XX, YY, ZZ2, s, t0;
   fu_add(s, p.X, p.Y);

@@ -90,6 +90,47 @@ def sq_terms(double, fmax):
     return out
 
 
+# the classical 10-limb squaring's operand set: 2 f_0 .. 2 f_7, and for the wrapped terms 19 f_j on even limbs 6, 8 and
+# 38 f_j on odd limbs 5, 7, 9 (the factor 2 of a wrapped cross term rides in the premultiply constant, not in a second
+# doubling): thirteen scaled operands, against the eighteen of sq_terms' power-of-two split
+SQ13 = [{1, 2} | ({19} if i in (6, 8) else set()) | ({38} if i in (5, 7, 9) else set()) for i in range(8)] + [{1, 19}, {1, 38}]
+# the same for the doubled square 2 f^2: the extra factor 2 rides in the premultiply constant too (38 f_j, 76 f_j) and in
+# 2 f_8, 2 f_9; only the unwrapped odd*odd cross terms (coefficient 8) need a second doubling, of f_1 and f_3: seventeen
+SQ17 = [{1, 2} | ({4} if i in (1, 3) else set()) | ({38} if i in (6, 8) else set()) | ({76} if i in (5, 7, 9) else set())
+        for i in range(10)]
+
+
+def sq_terms13(double, fmax):
+    """sq_terms with the scaled operands restricted to SQ13 (SQ17 for the doubled square); None where a scaled operand
+    of the class `fmax` would pass 2^32 (38 f_j with 4.5-unit odd limbs)"""
+    out = []
+    sets = SQ17 if double else SQ13
+    for i in range(10):
+        for j in range(i, 10):
+            c = (1 if i == j else 2) * (2 if (i % 2 == 1 and j % 2 == 1) else 1) * (2 if double else 1)
+            k = i + j
+            if k >= 10:
+                c *= 19
+                k -= 10
+            ab = [(a, c // a) for a in sorted(sets[i], reverse=double) if c % a == 0 and c // a in sets[j]]
+            ab = [(a, b) for (a, b) in ab if a * fmax[i] <= U32 and b * fmax[j] <= U32]
+            if not ab:
+                return None
+            out.append((k, i, ab[0][0], j, ab[0][1]))
+    return out
+
+
+def sq_cols(double, fmax):
+    """(columns, operand-set name) of a squaring for the input class `fmax`: the thirteen-operand set where it fits"""
+    t = sq_terms13(double, fmax)
+    return (build_cols(t), "17" if double else "13") if t else (build_cols(sq_terms(double, fmax)), "pow2")
+
+
+def n_scaled(cols):
+    return len({(i, a) for col in cols for (i, a, j, b) in col if a != 1} |
+               {(j, b) for col in cols for (i, a, j, b) in col if b != 1})
+
+
 def build_cols(terms):
     cols = [[] for _ in range(10)]
     for (k, i, a, j, b) in terms:
@@ -133,7 +174,8 @@ def units(u, odd_u=None, l9=None, slack=1 << 16):
 # column sums only.
 MUL_F = units(4.0, 4.5, 6.0)     # operand f of fu_mul
 MUL_G = units(3.0, 4.5, 6.0)     # operand g of fu_mul (premultiplied by 19)
-SQ_IN = MUL_G                    # operand of fu_sq / fu_sq2
+SQ_WIDE = MUL_G                  # the widest operand any squaring is offered; each squaring's own class is the limb-wise
+                                 # maximum over its sites (Model.sq_class), which decides its operand set
 
 
 def fmax_add(*xs):
@@ -174,6 +216,7 @@ class Model:
 
     def __init__(self, carried):
         self.C = carried
+        self.sq_sites = {False: [], True: []}    # [double]: (input maxima, where, narrow) of every fu_sq / fu_sq2 site
 
     def mul(self, f, g, where, narrow=False):
         assert all(f[i] <= MUL_F[i] for i in range(10)), (where, "f", f)
@@ -182,11 +225,20 @@ class Model:
             assert prove(MCOLS, f, g, where)[1] < 2**32, where
         return self.C
 
-    def sq(self, f, where, narrow=False, double=False):
-        assert all(f[i] <= SQ_IN[i] for i in range(10)), (where, f)
-        if narrow:
-            assert prove(build_cols(sq_terms(double, SQ_IN)), f, f, where)[1] < 2**32, where
+    def sq(self, f, where, narrow=False, double=False, carried=False):
+        """carried: a fu_sqc / fu_sqc_x2 site (input within the carried class, one-MAD wrap proven for that class);
+        double: fu_sq2; otherwise fu_sq / fu_sq_x2. Their classes are the limb-wise maxima over their sites (sq_class)"""
+        if carried:
+            assert not double and all(f[i] <= self.C[i] for i in range(10)), (where, f)
+            return self.C
+        assert all(f[i] <= SQ_WIDE[i] for i in range(10)), (where, f)
+        self.sq_sites[double].append((f, where, narrow))
+        if narrow:      # the top carry depends on the term coefficients only, not on how a term's factor is split
+            assert prove(build_cols(sq_terms(double, SQ_WIDE)), f, f, where)[1] < 2**32, where
         return self.C
+
+    def sq_class(self, double):
+        return [max(f[i] for (f, _, _) in self.sq_sites[double]) for i in range(10)]
 
 
 def pcarry_even(x):
@@ -208,7 +260,7 @@ def check_group_law(C, K):
     #     N1 = XX + YY + K - t0 (= -2XY), D1 = XX + K - YY (= X^2 - Y^2), N2 = XX + YY, D2 = ZZ2 + D1, even-carried
     X = Y = Z = C
     s = add(X, Y)
-    XX = m.sq(X, "dbl XX", True); YY = m.sq(Y, "dbl YY", True)
+    XX = m.sq(X, "dbl XX", carried=True); YY = m.sq(Y, "dbl YY", carried=True)
     t0 = m.sq(s, "dbl (X+Y)^2", True); ZZ2 = m.sq(Z, "dbl 2Z^2", True, True)
     N2 = add(XX, YY)
     assert dom(KC, t0) and dom(KC, YY)
@@ -265,7 +317,7 @@ def check_group_law(C, K):
 
     def j_dbl(P, nm):                        # gu_p2_dbl of (X, Y, Z)
         X, Y, Z = P[:3]
-        m.sq(X, nm + " XX", True); m.sq(Y, nm + " YY", True)
+        m.sq(X, nm + " XX", carried=True); m.sq(Y, nm + " YY", carried=True)
         m.sq(add(X, Y), nm + " (X+Y)^2", True); m.sq(Z, nm + " 2Z^2", True, True)
         return dbl
 
@@ -282,7 +334,7 @@ def check_group_law(C, K):
     m.sq(v, "decode v^2"); m.mul(C, v, "decode v^3"); m.mul(C, u, "decode u v^7")
     m.mul(u, C, "decode u sqrt(-1)")
     m.mul(C, v, "decode v x^2")
-    return True
+    return m
 
 
 def emit_fn(name, colsets, is_mul, cheap_wrap):
@@ -433,33 +485,79 @@ def lit(limbs):
     return "{{" + ", ".join(f"0x{v:x}u" for v in limbs) + "}}"
 
 
-def main():
-    out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(
-        os.path.dirname(__file__), "..", "at2-node_amd", "csrc", "at2v_fu_gen.h")
+def squaring_classes():
+    """per-limb input maxima each squaring is proven for, by function name (tests/test_sq_operands_host.py draws its
+    inputs from them). The two-way functions take (class of f0, class of f1); fu_sq_sq2_n's one-MAD wraps hold at its
+    site only, the doubling: f0 = X + Y, f1 = Z."""
+    d = derive()
+    C, S, S2 = d["C"], d["SQ_IN"], d["SQ2_IN"]
+    return {"fu_sq": (S, S), "fu_sq2": (S2, S2), "fu_sqc": (C, C), "fu_sq_x2": (S, S), "fu_sq_sq2": (S, S2),
+            "fu_sq_sq2_n": (fmax_add(C, C), C), "fu_sqc_x2": (C, C)}
+
+
+def derive():
+    """the proofs, in order: classes, spill, carried class, subtraction constants, group law, the squarings' sets"""
     mcols = build_cols(mul_terms())
-    scols = build_cols(sq_terms(False, SQ_IN))
-    s2cols = build_cols(sq_terms(True, SQ_IN))
     wm, c9m, spm = prove(mcols, MUL_F, MUL_G, "mul")
-    ws, c9s, sps = prove(scols, SQ_IN, SQ_IN, "sq")
-    ws2, c9s2, sps2 = prove(s2cols, SQ_IN, SQ_IN, "sq2")
-    spill = max(spm, sps, sps2)
+    # the limb-1 spill of the carried class is taken at the widest classes, the doubled square's included, although
+    # every squaring's own class is narrower: the carried class and the constants built on it stay where they were
+    spill = max(spm, prove(build_cols(sq_terms(True, SQ_WIDE)), SQ_WIDE, SQ_WIDE, "sq2 wide")[2])
     # carried output class; it must lie inside every input class
     C = [(1 << W[i]) - 1 for i in range(10)]
     C[1] += spill
-    assert all(C[i] <= MUL_G[i] and C[i] <= SQ_IN[i] for i in range(10))
+    assert all(C[i] <= MUL_G[i] for i in range(10))
     K = {"C": kconst(C), "2C": kconst(fmax_add(C, C))}
     pm1 = carried_limbs(P - 1)
     K["PM1"] = pm1
     assert val(pm1) == P - 1
-    check_group_law(C, K)
+    model = check_group_law(C, K)
+    # fu_sq / fu_sq_x2: the class its sites need (the doubling's (X+Y)^2 and the decode's v^2: sums of two carried
+    # elements), and the operand set that class allows; fu_sq2: the doubling's Z, carried; fu_sqc / fu_sqc_x2: carried
+    SQ_IN, SQ2_IN = model.sq_class(False), model.sq_class(True)
+    assert all(C[i] <= SQ_IN[i] <= SQ_WIDE[i] and C[i] <= SQ2_IN[i] <= SQ_WIDE[i] for i in range(10))
+    scols, sset = sq_cols(False, SQ_IN)
+    s2cols, s2set = sq_cols(True, SQ2_IN)
+    sccols, scset = sq_cols(False, C)
+    ws, c9s, sps = prove(scols, SQ_IN, SQ_IN, "sq")
+    ws2, c9s2, sps2 = prove(s2cols, SQ2_IN, SQ2_IN, "sq2")
+    wsc, c9sc, spsc = prove(sccols, C, C, "sqc")
+    assert max(sps, sps2, spsc) <= spill, "a squaring's wrap carry leaves the carried class"
+    for double, cols in ((False, scols), (True, s2cols)):
+        for (f, where, narrow) in model.sq_sites[double]:
+            assert not narrow or prove(cols, f, f, where)[1] < 2**32, where
+    sq2_units = [round(SQ2_IN[i] / (1 << W[i]), 2) for i in range(10)]
+    sq_units = [round(SQ_IN[i] / (1 << W[i]), 2) for i in range(10)]
+    return dict(locals())
+
+
+def main():
+    out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(
+        os.path.dirname(__file__), "..", "at2-node_amd", "csrc", "at2v_fu_gen.h")
+    d = derive()
+    mcols, scols, s2cols, sccols = d["mcols"], d["scols"], d["s2cols"], d["sccols"]
+    sset, s2set, scset, sq_units, sq2_units, spill, C, K = (
+        d[k] for k in ("sset", "s2set", "scset", "sq_units", "sq2_units", "spill", "C", "K"))
+    wm, c9m, ws, c9s, ws2, c9s2, wsc, c9sc = (d[k] for k in ("wm", "c9m", "ws", "c9s", "ws2", "c9s2", "wsc", "c9sc"))
+    setname = {"13": "thirteen operands (2 f_0..2 f_7, 19 f_6, 19 f_8, 38 f_5, 38 f_7, 38 f_9)",
+               "17": "seventeen operands (2 f_0..2 f_9, 4 f_1, 4 f_3, 38 f_6, 38 f_8, 76 f_5, 76 f_7, 76 f_9)",
+               "pow2": "power-of-two operands (f_i, 2 f_i, 4 f_i and 19 f_j)"}
 
     hdr = []
     hdr.append("// GENERATED by tools/gen_fu.py -- do not edit. Regenerate: python3 tools/gen_fu.py")
     hdr.append("// Bound proof (per limb, tools/gen_fu.py): fu_mul f within 4 carried units on even limbs, 4.5 on odd ones")
-    hdr.append("// (limb 9: 6); fu_mul g and fu_sq operands within 3 on even limbs (x19 premultiplied); scaled operands < 2^32; columns with carry-in: mul 2^{wm.bit_length()}, sq 2^{ws.bit_length()}, "
-               f"sq2 2^{ws2.bit_length()} (< 2^64);")
-    hdr.append(f"// top carry mul 2^{c9m.bit_length()}, sq 2^{c9s.bit_length()}, sq2 2^{c9s2.bit_length()}; "
-               f"carried output: limb i < 2^W[i], limb 1 <= 2^25 - 1 + {spill}.")
+    hdr.append("// (limb 9: 6); fu_mul g operands within 3 on even limbs (x19 premultiplied); fu_sq / fu_sq_x2 operands within")
+    hdr.append(f"// {max(sq_units[0::2])} units on even limbs and {max(sq_units[1::2])} on odd ones, fu_sq2 operands within "
+               f"{max(sq2_units[0::2])} and {max(sq2_units[1::2])} (the largest input of their")
+    hdr.append(f"// sites, check_group_law); fu_sqc / fu_sqc_x2 operands carried. Scaled operands < 2^32; columns with carry-in: mul 2^{wm.bit_length()}, "
+               f"sq 2^{ws.bit_length()}, sqc 2^{wsc.bit_length()},")
+    hdr.append(f"// sq2 2^{ws2.bit_length()} (<= 2^64 - 1); top carry mul 2^{c9m.bit_length()}, sq 2^{c9s.bit_length()}, "
+               f"sqc 2^{c9sc.bit_length()}, sq2 2^{c9s2.bit_length()}; carried output: limb i < 2^W[i],")
+    hdr.append(f"// limb 1 <= 2^25 - 1 + {spill} (the spill is taken at 3 / 4.5 / 6-unit squaring operands, wider than any site).")
+    hdr.append("// Scaled operands of the squarings, chosen per input class (sq_cols): the thirteen-operand set needs 38 f_j < 2^32")
+    hdr.append("// on odd limbs 5, 7, 9, the doubled square's seventeen 76 f_j < 2^32; a wider class keeps the power-of-two split:")
+    hdr.append(f"//   fu_sqc, fu_sqc_x2 (carried): {setname[scset]}, {n_scaled(sccols)} scaled;")
+    hdr.append(f"//   fu_sq, fu_sq_x2, h0 of fu_sq_sq2 / fu_sq_sq2_n: {setname[sset]}, {n_scaled(scols)} scaled;")
+    hdr.append(f"//   fu_sq2, h1 of fu_sq_sq2 / fu_sq_sq2_n: {setname[s2set]}, {n_scaled(s2cols)} scaled.")
     hdr.append("// The group law of at2v_gu.h is checked against these classes (check_group_law).")
     hdr.append("#pragma once")
     hdr.append('#include "at2v_fu_base.h"')
@@ -468,10 +566,8 @@ def main():
     hdr.append(f"// mul: {sum(len(c) for c in mcols)} v_mad_u64_u32; sq: {sum(len(c) for c in scols)}; "
                f"sq2: {sum(len(c) for c in s2cols)}")
     # variants for carried inputs (exponentiation chains): the top carry stays below 2^32, so the wrap is one MAD
-    sccols = build_cols(sq_terms(False, C))
-    wsc, c9sc, spsc = prove(sccols, C, C, "sqc")
     wmc, c9mc, spmc = prove(mcols, C, C, "mulc")
-    assert c9sc < 2**32 and c9mc < 2**32 and max(spsc, spmc) <= spill
+    assert c9sc < 2**32 and c9mc < 2**32 and spmc <= spill
     cw_m, cw_s, cw_s2 = c9m < 2**32, c9s < 2**32, c9s2 < 2**32
     hdr.append(emit_fn("fu_mul", [mcols], True, [cw_m]))
     hdr.append(emit_fn("fu_sq", [scols], False, [cw_s]))
