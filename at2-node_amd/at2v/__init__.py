@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = ("at2v_abi_version", "at2v_create", "at2v_destroy", "at2v_ver
                     "at2v_gen_records_senders_device", "at2v_gen_records_keys_device", "at2v_sign_batch", "at2v_get_info", "at2v_decode_points",
                     "at2v_comm_get_unique_id", "at2v_comm_init_rank", "at2v_verify_shard_gather_device",
                     "at2v_verify_batch_sharded", "at2v_verify_batch_submit", "at2v_verify_batch_wait",
+                    "at2v_host_alloc", "at2v_host_free", "at2v_host_register", "at2v_host_unregister",
                     "at2v_queue_create", "at2v_queue_destroy", "at2v_queue_submit", "at2v_queue_flush",
                     "at2v_queue_poll", "at2v_queue_get_stats", "at2v_queue_reset_latency",
                     "at2v_pack_send_asset",
@@ -71,7 +72,7 @@ class VerifyError(Exception):
         self.reason = reason
 
 
-ABI_VERSION = 8  # include/at2v.h AT2V_ABI_VERSION: the struct layouts below are those of this version
+ABI_VERSION = 9  # include/at2v.h AT2V_ABI_VERSION: the struct layouts below are those of this version
 E_PEER = -7      # AT2V_E_PEER: another rank of the communicator failed this collective batch
 
 
@@ -101,7 +102,8 @@ class _Info(ctypes.Structure):
                 ("cpu_batches", ctypes.c_uint64), ("cpu_fallbacks", ctypes.c_uint64),
                 ("cache_sightings", ctypes.c_uint64), ("cache_built", ctypes.c_uint64),
                 ("cache_build_us", ctypes.c_uint64), ("cache_record_hits", ctypes.c_uint64),
-                ("experiments", ctypes.c_uint64), ("host_chunks", ctypes.c_uint64)]
+                ("experiments", ctypes.c_uint64), ("host_chunks", ctypes.c_uint64),
+                ("host_direct_bytes", ctypes.c_uint64), ("host_staged_bytes", ctypes.c_uint64)]
 
 
 UNIQUE_ID_BYTES = 128  # AT2V_UNIQUE_ID_BYTES (RCCL ncclUniqueId)
@@ -140,6 +142,14 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.at2v_verify_batch_submit.restype = ctypes.c_int
     lib.at2v_verify_batch_wait.argtypes = [P, ctypes.c_uint64]
     lib.at2v_verify_batch_wait.restype = ctypes.c_int
+    lib.at2v_host_alloc.argtypes = [P, ctypes.c_size_t, ctypes.POINTER(P)]
+    lib.at2v_host_alloc.restype = ctypes.c_int
+    lib.at2v_host_free.argtypes = [P, P]
+    lib.at2v_host_free.restype = ctypes.c_int
+    lib.at2v_host_register.argtypes = [P, P, ctypes.c_size_t]
+    lib.at2v_host_register.restype = ctypes.c_int
+    lib.at2v_host_unregister.argtypes = [P, P]
+    lib.at2v_host_unregister.restype = ctypes.c_int
     lib.at2v_verify_batch_device.argtypes = [P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P, P]
     lib.at2v_verify_batch_device.restype = ctypes.c_int
     lib.at2v_verify_one.argtypes = [P, P, P, ctypes.c_size_t]
@@ -241,6 +251,15 @@ def launch_streams(count: int = 2, device: Optional[int] = None) -> list:
     return out
 
 
+class _PinnedBlock:
+    """Memory handed out by at2v_host_alloc, exposed through the array interface: the array made from it (and every
+    view of that array) holds this object, and this object holds the verifier."""
+
+    def __init__(self, owner: "BatchVerifier", address: int, nbytes: int):
+        self.owner, self.address, self.nbytes = owner, address, nbytes
+        self.__array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (address, False), "version": 3}
+
+
 class PendingBatch:
     """A submitted host-buffer batch (BatchVerifier.submit_batch): its ticket, verdict words and the arrays the library
     reads until the wait."""
@@ -274,11 +293,15 @@ class BatchVerifier:
         h = ctypes.c_void_p()
         _check(self._lib.at2v_create(ctypes.byref(opts), ctypes.byref(h)), "at2v_create")
         self._h = h
+        self._registered = {}  # host_register: address -> the array (kept alive while the library may read it)
 
     def close(self):
+        """at2v_destroy: also frees what host_alloc handed out (arrays made from it must not be used afterwards) and
+        unregisters what is still registered"""
         if getattr(self, "_h", None):
             self._lib.at2v_destroy(self._h)
             self._h = None
+            self._registered = {}
 
     def __del__(self):
         try:
@@ -297,8 +320,48 @@ class BatchVerifier:
         _check(self._lib.at2v_get_info(self._h, ctypes.byref(inf)), "at2v_get_info")
         return {f: getattr(inf, f) for f, _ in _Info._fields_}
 
-    def verify_batch(self, pk: np.ndarray, sig: np.ndarray, msg: np.ndarray, msg_off: np.ndarray) -> np.ndarray:
-        """host arrays -> bool[n] verdicts"""
+    # ---- pinned host memory (include/at2v.h at2v_host_*): records that lie in it are uploaded without a host copy
+    def host_alloc(self, nbytes: int) -> np.ndarray:
+        """at2v_host_alloc: `nbytes` of pinned memory (64-byte aligned, visible to every device of the context; plain
+        host memory on a CPU context) as a uint8 array. Carve pk / sig / msg (and the verdict words) out of it with
+        slices and views: verify_batch uploads what lies in it straight from there. The array keeps the verifier
+        alive; host_free (or close) releases the memory."""
+        p = ctypes.c_void_p()
+        _check(self._lib.at2v_host_alloc(self._h, int(nbytes), ctypes.byref(p)), "at2v_host_alloc")
+        return np.asarray(_PinnedBlock(self, p.value, int(nbytes)))
+
+    def host_free(self, arr: np.ndarray) -> None:
+        """at2v_host_free: `arr` is the array host_alloc returned (or a view that starts at its first byte); it and
+        its views must not be used afterwards"""
+        _check(self._lib.at2v_host_free(self._h, arr.ctypes.data), "at2v_host_free")
+
+    def host_register(self, arr: np.ndarray) -> None:
+        """at2v_host_register: pin the C-contiguous array's bytes in place (any alignment) and make them known to the
+        context. The verifier holds the array until host_unregister."""
+        if not arr.flags.c_contiguous or arr.nbytes == 0:
+            raise ValueError("host_register needs a non-empty C-contiguous array")
+        _check(self._lib.at2v_host_register(self._h, arr.ctypes.data, arr.nbytes), "at2v_host_register")
+        self._registered[arr.ctypes.data] = arr
+
+    def host_unregister(self, arr: np.ndarray) -> None:
+        """at2v_host_unregister: `arr` starts at the first byte of a registered array"""
+        _check(self._lib.at2v_host_unregister(self._h, arr.ctypes.data), "at2v_host_unregister")
+        self._registered.pop(arr.ctypes.data, None)
+
+    @staticmethod
+    def _verdict_words(n: int, words: Optional[np.ndarray]) -> np.ndarray:
+        """the caller's verdict words (uint32, C-contiguous, at least ceil(n/32)), or fresh ones"""
+        if words is None:
+            return np.zeros(max(1, (n + 31) // 32), dtype=np.uint32)
+        if words.dtype != np.uint32 or not words.flags.c_contiguous or words.size < max(1, (n + 31) // 32):
+            raise ValueError("words must be a C-contiguous uint32 array of at least ceil(n/32) entries")
+        return words
+
+    def verify_batch(self, pk: np.ndarray, sig: np.ndarray, msg: np.ndarray, msg_off: np.ndarray,
+                     words: Optional[np.ndarray] = None) -> np.ndarray:
+        """host arrays -> bool[n] verdicts. Arrays that are uint8 (msg_off: uint32) and C-contiguous are passed as they
+        are, so records in host_alloc / host_register memory are uploaded from there. words: the verdict words go into
+        this uint32 array (e.g. a view of host_alloc memory) instead of a fresh one."""
         pk = np.ascontiguousarray(pk, dtype=np.uint8)
         sig = np.ascontiguousarray(sig, dtype=np.uint8)
         msg = np.ascontiguousarray(msg, dtype=np.uint8).reshape(-1)
@@ -306,13 +369,14 @@ class BatchVerifier:
         n = len(msg_off) - 1
         if pk.size != 32 * n or sig.size != 64 * n:
             raise ValueError("pk/sig/msg_off sizes disagree")
-        words = np.zeros(max(1, (n + 31) // 32), dtype=np.uint32)
+        words = self._verdict_words(n, words)
         msg_arg = msg if msg.size else np.zeros(1, np.uint8)
         _check(self._lib.at2v_verify_batch(self._h, _ptr(pk), _ptr(sig), _ptr(msg_arg), _ptr(msg_off), n,
                                            _ptr(words)), "at2v_verify_batch")
         return unpack_verdicts(words, n)
 
-    def submit_batch(self, pk: np.ndarray, sig: np.ndarray, msg: np.ndarray, msg_off: np.ndarray) -> "PendingBatch":
+    def submit_batch(self, pk: np.ndarray, sig: np.ndarray, msg: np.ndarray, msg_off: np.ndarray,
+                     words: Optional[np.ndarray] = None) -> "PendingBatch":
         """at2v_verify_batch_submit: stage the batch and enqueue its verification; returns the pending call (it holds
         the arrays until wait_batch). At most two in flight per context."""
         pk = np.ascontiguousarray(pk, dtype=np.uint8)
@@ -322,7 +386,7 @@ class BatchVerifier:
         n = len(msg_off) - 1
         if pk.size != 32 * n or sig.size != 64 * n:
             raise ValueError("pk/sig/msg_off sizes disagree")
-        words = np.zeros(max(1, (n + 31) // 32), dtype=np.uint32)
+        words = self._verdict_words(n, words)
         msg_arg = msg if msg.size else np.zeros(1, np.uint8)
         t = ctypes.c_uint64(0)
         _check(self._lib.at2v_verify_batch_submit(self._h, _ptr(pk), _ptr(sig), _ptr(msg_arg), _ptr(msg_off), n,
@@ -356,7 +420,8 @@ class BatchVerifier:
                                                          d_bitmap, stream or None),
                "at2v_verify_shard_gather_device")
 
-    def verify_batch_sharded(self, pk: np.ndarray, sig: np.ndarray, msg: np.ndarray, msg_off: np.ndarray) -> np.ndarray:
+    def verify_batch_sharded(self, pk: np.ndarray, sig: np.ndarray, msg: np.ndarray, msg_off: np.ndarray,
+                             words: Optional[np.ndarray] = None) -> np.ndarray:
         """the node batch (same on every rank) -> bool[n] verdicts of the whole batch on every rank"""
         pk = np.ascontiguousarray(pk, dtype=np.uint8)
         sig = np.ascontiguousarray(sig, dtype=np.uint8)
@@ -365,7 +430,7 @@ class BatchVerifier:
         n = len(msg_off) - 1
         if pk.size != 32 * n or sig.size != 64 * n:
             raise ValueError("pk/sig/msg_off sizes disagree")
-        words = np.zeros(max(1, (n + 31) // 32), dtype=np.uint32)
+        words = self._verdict_words(n, words)
         msg_arg = msg if msg.size else np.zeros(1, np.uint8)
         _check(self._lib.at2v_verify_batch_sharded(self._h, _ptr(pk), _ptr(sig), _ptr(msg_arg), _ptr(msg_off), n,
                                                    _ptr(words)), "at2v_verify_batch_sharded")

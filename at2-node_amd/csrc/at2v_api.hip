@@ -35,6 +35,7 @@
 #include "at2v_cache.h"
 #include "at2v_cpu.h"
 #include "at2v_env.h"
+#include "at2v_hostmem.h"
 #include "at2v_launch.h"
 #include "at2v_reason_launch.h"
 #include "at2v_shard.h"
@@ -217,6 +218,11 @@ struct at2v_ctx {
   bool pipe_trace = false;  // test hook AT2V_TEST_PIPE_TRACE: per host-buffer call, where the host's time went (stderr)
   double tr_wait = 0, tr_copy = 0, tr_enq = 0;  // seconds, this call
   uint64_t host_chunks = 0;  // chunks staged by host-buffer calls (at2v_info.host_chunks)
+  // pinned host ranges handed over through at2v_host_alloc / at2v_host_register: a slice of pk, sig or msg that lies
+  // wholly inside one of them is uploaded from the caller's memory, without the copy into a staging slot (issue_chunk)
+  at2v::HostRegistry hostmem;
+  uint64_t host_direct_bytes = 0, host_staged_bytes = 0;  // at2v_info: pk/sig/msg bytes uploaded either way
+  bool hsa_ref = false;  // at2v_host_alloc / _register took their reference on the HSA runtime (hsa_init)
   uint32_t test_fail_launches = 0;  // AT2V_TEST_FAIL_LAUNCH (tests only): that many launches fail before the kernel
   bool partition = true;  // cached launches above pair_max classify, then verify hits and misses apart (AT2V_CACHE_PARTITION)
   ncclComm_t comm = nullptr;  // at2v_comm_init_rank (one rank per process, the context's first device)
@@ -771,7 +777,8 @@ hipError_t flush_chunk(at2v_ctx* ctx, Shard& s) {
 // shard's device bitmap, zeroed by the launch first). Current device = s.device. The four parts (pk, sig + offsets,
 // messages) are copied and submitted one after the other, so the DMA of one overlaps the host copy of the next; then the
 // previous chunk is launched (its uploads had this chunk's host copy to finish). The first chunk of a call (`first`)
-// is launched at once: it is the pipeline's fill.
+// is launched at once: it is the pipeline's fill. A slice of pk, sig or msg that lies in pinned memory the context knows
+// (ctx->hostmem) skips the slot: its upload is submitted from the caller's memory, with no host copy.
 hipError_t issue_chunk(at2v_ctx* ctx, Shard& s, at2v::CpuPool* copier, const uint8_t* pk, const uint8_t* sig,
                        const uint8_t* msg, const uint32_t* msg_off, size_t a, size_t c, uint32_t* d_words,
                        bool throughput, bool first) {
@@ -797,10 +804,23 @@ hipError_t issue_chunk(at2v_ctx* ctx, Shard& s, at2v::CpuPool* copier, const uin
   }
   if (e != hipSuccess) return e;
   const auto t1 = clk::now();
-  hsa_signal_store_screlease(sl.uploaded, mb ? 3 : 2);  // the parts below, each decrements it when done
-  auto upload = [&](size_t at, size_t len) {
-    return hsa_err(hsa_amd_memory_async_copy(d + at, p.gpu, sl.host + at, p.cpu, len, 0, nullptr, sl.uploaded));
+  // Per array: the address the DMA engine reads the chunk's slice from when it lies wholly inside one known pinned range
+  // (at2v_host_alloc / at2v_host_register), else nullptr: the slice is copied into the slot first, as every slice was
+  // before ABI 9. The offsets are always staged (rebased on the host), so a chunk that is direct in all three arrays
+  // still takes its slot, and sig + offsets are two uploads when sig is direct.
+  auto dma_src = [&](const uint8_t* src, size_t len) -> const uint8_t* {
+    const at2v::HostRange* r = ctx->hostmem.find(src, len);
+    return r ? reinterpret_cast<const uint8_t*>(r->dma + (reinterpret_cast<uintptr_t>(src) - r->base)) : nullptr;
   };
+  const uint8_t* pk_src = dma_src(pk + a * 32, c * 32);
+  const uint8_t* sig_src = dma_src(sig + a * 64, c * 64);
+  const uint8_t* msg_src = mb ? dma_src(msg + mb0, mb) : nullptr;
+  // the uploads submitted below, each decrements the signal when done
+  hsa_signal_store_screlease(sl.uploaded, 1 + (sig_src ? 2 : 1) + (mb ? 1 : 0));
+  auto upload_from = [&](size_t at, const uint8_t* src, size_t len) {
+    return hsa_err(hsa_amd_memory_async_copy(d + at, p.gpu, src, p.cpu, len, 0, nullptr, sl.uploaded));
+  };
+  auto upload = [&](size_t at, size_t len) { return upload_from(at, sl.host + at, len); };
   // between copy batches: the pending (previous) chunk is launched as soon as its uploads have landed, so the device
   // does not wait for this chunk's whole host copy (the pipeline's fill: the second chunk's launch)
   hipError_t ef = hipSuccess;
@@ -809,18 +829,32 @@ hipError_t issue_chunk(at2v_ctx* ctx, Shard& s, at2v::CpuPool* copier, const uin
       ef = flush_chunk(ctx, s);
   };
   CopyJob job;
-  job.add(sl.host, pk + a * 32, c * 32);
-  run_copy(copier, job, c * 32, poll);
-  e = upload(0, c * 32);
-  job.add(sl.host + L.sig, sig + a * 64, c * 64);
+  if (pk_src) {
+    e = upload_from(0, pk_src, c * 32);
+  } else {
+    job.add(sl.host, pk + a * 32, c * 32);
+    run_copy(copier, job, c * 32, poll);
+    e = upload(0, c * 32);
+  }
+  if (sig_src) {
+    if (e == hipSuccess) e = upload_from(L.sig, sig_src, c * 64);
+  } else {
+    job.add(sl.host + L.sig, sig + a * 64, c * 64);
+  }
   job.add_offsets((uint32_t*)(sl.host + L.off), msg_off + a, c + 1, mb0);
-  run_copy(copier, job, c * 68, poll);
-  if (e == hipSuccess) e = upload(L.sig, L.msg - L.sig);
-  if (mb) {
+  run_copy(copier, job, sig_src ? (c + 1) * 4 : c * 68, poll);
+  const size_t off_at = sig_src ? L.off : L.sig;
+  if (e == hipSuccess) e = upload(off_at, L.msg - off_at);
+  if (mb && msg_src) {
+    if (e == hipSuccess) e = upload_from(L.msg, msg_src, mb);
+  } else if (mb) {
     job.add(sl.host + L.msg, msg + mb0, mb);
     run_copy(copier, job, mb, poll);
     if (e == hipSuccess) e = upload(L.msg, mb);
   }
+  const size_t direct = (pk_src ? c * 32 : 0) + (sig_src ? c * 64 : 0) + (msg_src ? mb : 0);
+  ctx->host_direct_bytes += direct;
+  ctx->host_staged_bytes += c * 96 + mb - direct;
   if (e == hipSuccess) e = ef;
   if (e != hipSuccess) {  // (a submit failed: nothing waits for this slot's parts any more; the call fails)
     hsa_signal_store_screlease(sl.uploaded, 0);
@@ -1059,6 +1093,17 @@ void at2v_destroy(at2v_ctx* ctx) {
     s.reasons.release();
     if (s.stream) (void)hipStreamDestroy(s.stream);
   }
+  // the pinned host ranges still known (every upload from them has landed: free_pipe waited for the slots' signals)
+  for (const at2v::HostRange& r : ctx->hostmem.ranges()) {
+    void* p = reinterpret_cast<void*>(r.base);
+    if (ctx->shards.empty()) {
+      if (r.owned) std::free(p);
+    } else if (r.owned) {
+      (void)hipHostFree(p);
+    } else {
+      (void)hsa_amd_memory_unlock(p);
+    }
+  }
   at2v::cpu_pool_destroy(ctx->cpu);
   at2v::cpu_pool_destroy(ctx->copier);
   delete ctx;
@@ -1268,6 +1313,170 @@ int at2v_verify_batch(at2v_ctx* ctx, const uint8_t* pk, const uint8_t* sig, cons
   hc.active = false;
   (void)hipSetDevice(prev);
   return hc.rc;
+}
+
+// ---- pinned host memory (at2v_host_alloc / _free / _register / _unregister) ----
+// A CPU context only records the ranges: every hip* / hsa* call below is behind `ctx->shards.empty()`.
+
+namespace {
+
+void* pointer_info_alloc(size_t bytes) { return std::malloc(bytes); }
+
+// What the runtime says about the pinned range [p, p + bytes) of a GPU context: AT2V_OK and the address the DMA engine
+// is given for p (the range's agent address; for memory pinned in place it differs from the host address), or
+// AT2V_E_INVALID unless the runtime reports the whole range as one pinned allocation (its own, or locked in place)
+// that every shard's device can reach. A copy from an address a device cannot read is a GPU fault, not an error code:
+// this check keeps such a copy from ever being submitted.
+bool hsa_ready(at2v_ctx* ctx) {  // (HIP already initialised the runtime; hsa_init only takes a reference, as in ensure_pipe)
+  if (!ctx->hsa_ref) ctx->hsa_ref = hsa_init() == HSA_STATUS_SUCCESS;
+  return ctx->hsa_ref;
+}
+
+// the device agents of the context's shards, each once (aliased shards share one): the owners of their B tables
+bool shard_agents(at2v_ctx* ctx, std::vector<hsa_agent_t>& out) {
+  for (const Shard& s : ctx->shards) {
+    hsa_amd_pointer_info_t di;
+    std::memset(&di, 0, sizeof di);
+    di.size = sizeof di;
+    if (hsa_amd_pointer_info(s.btab.p, &di, nullptr, nullptr, nullptr) != HSA_STATUS_SUCCESS || !di.agentOwner.handle)
+      return false;
+    bool seen = false;
+    for (const hsa_agent_t& a : out) seen = seen || a.handle == di.agentOwner.handle;
+    if (!seen) out.push_back(di.agentOwner);
+  }
+  return !out.empty();
+}
+
+// `locked`: what hsa_amd_memory_lock returned for p (at2v_host_register), nullptr for the runtime's own allocation. On
+// an MI355X the runtime maps memory locked in place into the devices at its own address (shared virtual memory) and
+// hsa_amd_pointer_info does not know such a range (type unknown; memory pinned by hipHostRegister reads the same). The
+// runtime's report is then its access query: every device must have access to every page of the range.
+int pinned_range_dma(at2v_ctx* ctx, const void* p, size_t bytes, const void* locked, uintptr_t* dma) {
+  if (!hsa_ready(ctx)) return AT2V_E_HIP;
+  std::vector<hsa_agent_t> gpus;
+  if (!shard_agents(ctx, gpus)) return AT2V_E_HIP;
+  hsa_amd_pointer_info_t info;
+  std::memset(&info, 0, sizeof info);
+  info.size = sizeof info;
+  uint32_t na = 0;
+  hsa_agent_t* acc = nullptr;
+  if (hsa_amd_pointer_info(p, &info, pointer_info_alloc, &na, &acc) != HSA_STATUS_SUCCESS) return AT2V_E_INVALID;
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), hb = reinterpret_cast<uintptr_t>(info.hostBaseAddress);
+  if (info.type == HSA_EXT_POINTER_TYPE_UNKNOWN && locked == p) {
+    std::free(acc);
+    const uintptr_t page = 4096, lo = a & ~(page - 1), hi = (a + bytes + page - 1) & ~(page - 1);
+    for (const hsa_agent_t& g : gpus) {
+      hsa_amd_svm_attribute_pair_t q{HSA_AMD_SVM_ATTRIB_ACCESS_QUERY, g.handle};
+      if (hsa_amd_svm_attributes_get(reinterpret_cast<void*>(lo), hi - lo, &q, 1) != HSA_STATUS_SUCCESS) return AT2V_E_INVALID;
+      if (q.attribute != HSA_AMD_SVM_ATTRIB_AGENT_ACCESSIBLE && q.attribute != HSA_AMD_SVM_ATTRIB_AGENT_ACCESSIBLE_IN_PLACE)
+        return AT2V_E_INVALID;
+    }
+    *dma = a;
+    return AT2V_OK;
+  }
+  bool ok = (info.type == HSA_EXT_POINTER_TYPE_HSA || info.type == HSA_EXT_POINTER_TYPE_LOCKED) &&
+            info.agentBaseAddress && info.hostBaseAddress && hb <= a && a + bytes <= hb + info.sizeInBytes;
+  for (size_t g = 0; g < gpus.size() && ok; ++g) {
+    bool reach = false;
+    for (uint32_t i = 0; i < na; ++i) reach = reach || acc[i].handle == gpus[g].handle;
+    ok = reach;
+  }
+  std::free(acc);
+  if (!ok) return AT2V_E_INVALID;
+  *dma = reinterpret_cast<uintptr_t>(info.agentBaseAddress) + (a - hb);
+  if (locked && *dma != reinterpret_cast<uintptr_t>(locked)) return AT2V_E_INVALID;  // (the lock and the report disagree)
+  return AT2V_OK;
+}
+
+// Before a known range goes away: the host-buffer calls in flight complete (their results stay for their waits), and
+// every upload a failed call may have left behind has landed, so no DMA reads the range any more.
+void quiesce_host_calls(at2v_ctx* ctx) {
+  if (ctx->shards.empty()) return;
+  drain_host_calls(ctx);
+  for (Shard& s : ctx->shards)
+    if (s.pipe)
+      for (StageSlot& sl : s.pipe->slot)
+        if (sl.uploaded.handle) (void)wait_uploads(sl);
+}
+
+}  // namespace
+
+int at2v_host_alloc(at2v_ctx* ctx, size_t bytes, void** out) {
+  if (!ctx || !out) return AT2V_E_INVALID;
+  *out = nullptr;
+  if (bytes == 0 || bytes > (~(size_t)0 >> 1)) return AT2V_E_INVALID;
+  at2v::HostRange r;
+  r.len = bytes;
+  r.owned = true;
+  void* p = nullptr;
+  if (ctx->shards.empty()) {  // CPU context: plain host memory, no device is touched
+    p = std::aligned_alloc(64, (bytes + 63) & ~(size_t)63);
+    if (!p) return AT2V_E_OOM;
+    r.base = reinterpret_cast<uintptr_t>(p);
+    if (!ctx->hostmem.insert(r)) {
+      std::free(p);
+      return AT2V_E_INVALID;
+    }
+    *out = p;
+    return AT2V_OK;
+  }
+  // portable: pinned for and mapped to every device, whichever is current (page-aligned, so 64-byte aligned)
+  if (hipHostMalloc(&p, bytes, hipHostMallocPortable) != hipSuccess || !p) return AT2V_E_OOM;
+  r.base = reinterpret_cast<uintptr_t>(p);
+  int rc = pinned_range_dma(ctx, p, bytes, nullptr, &r.dma);
+  if (rc == AT2V_OK && !ctx->hostmem.insert(r)) rc = AT2V_E_INVALID;
+  if (rc != AT2V_OK) {
+    (void)hipHostFree(p);
+    return rc;
+  }
+  *out = p;
+  return AT2V_OK;
+}
+
+int at2v_host_free(at2v_ctx* ctx, void* p) {
+  if (!ctx || !p) return AT2V_E_INVALID;
+  const at2v::HostRange* r = ctx->hostmem.at(p);
+  if (!r || !r->owned) return AT2V_E_INVALID;
+  quiesce_host_calls(ctx);
+  ctx->hostmem.remove(p);
+  if (ctx->shards.empty()) {
+    std::free(p);
+    return AT2V_OK;
+  }
+  return hip_code(hipHostFree(p));
+}
+
+int at2v_host_register(at2v_ctx* ctx, void* p, size_t bytes) {
+  if (!ctx || !p || bytes == 0) return AT2V_E_INVALID;
+  at2v::HostRange r;
+  r.base = reinterpret_cast<uintptr_t>(p);
+  r.len = bytes;
+  if (r.base + bytes < r.base) return AT2V_E_INVALID;
+  if (ctx->shards.empty()) return ctx->hostmem.insert(r) ? AT2V_OK : AT2V_E_INVALID;  // CPU context: recorded only
+  // an overlap with a known range is refused before the runtime is asked to pin anything
+  if (!ctx->hostmem.insertable(r.base, r.len)) return AT2V_E_INVALID;
+  // Locked through the HSA runtime for exactly the devices of the context (what hipHostRegister does underneath, for
+  // every device). The lock returns the address the devices see the range at; the runtime's own report of the range
+  // must confirm it (pinned_range_dma), or the registration is refused.
+  std::vector<hsa_agent_t> gpus;
+  if (!hsa_ready(ctx) || !shard_agents(ctx, gpus)) return AT2V_E_HIP;
+  void* agent_ptr = nullptr;
+  if (hsa_amd_memory_lock(p, bytes, gpus.data(), (int)gpus.size(), &agent_ptr) != HSA_STATUS_SUCCESS || !agent_ptr)
+    return AT2V_E_OOM;
+  int rc = pinned_range_dma(ctx, p, bytes, agent_ptr, &r.dma);
+  if (rc == AT2V_OK && !ctx->hostmem.insert(r)) rc = AT2V_E_INVALID;
+  if (rc != AT2V_OK) (void)hsa_amd_memory_unlock(p);
+  return rc;
+}
+
+int at2v_host_unregister(at2v_ctx* ctx, void* p) {
+  if (!ctx || !p) return AT2V_E_INVALID;
+  const at2v::HostRange* r = ctx->hostmem.at(p);
+  if (!r || r->owned) return AT2V_E_INVALID;
+  quiesce_host_calls(ctx);
+  ctx->hostmem.remove(p);
+  if (ctx->shards.empty()) return AT2V_OK;
+  return hsa_amd_memory_unlock(p) == HSA_STATUS_SUCCESS ? AT2V_OK : AT2V_E_HIP;
 }
 
 int at2v_verify_batch_device(at2v_ctx* ctx, const uint8_t* d_pk, const uint8_t* d_sig, const uint8_t* d_msg,
@@ -1684,6 +1893,8 @@ int at2v_get_info(at2v_ctx* ctx, at2v_info* out) {
   out->cpu_fallbacks = ctx->cpu_fallbacks;
   out->experiments = library_experiments();
   out->host_chunks = ctx->host_chunks;
+  out->host_direct_bytes = ctx->host_direct_bytes;
+  out->host_staged_bytes = ctx->host_staged_bytes;
   if (ctx->shards.empty()) return AT2V_OK;  // CPU context: no device geometry
   const Shard& s = ctx->shards[0];
   out->num_gpus = (int)ctx->shards.size();

@@ -31,7 +31,7 @@ pub struct At2vLedger {
 
 /// include/at2v.h AT2V_ABI_VERSION: the layouts of the #[repr(C)] structs below. `BatchVerifier::new` and
 /// `Queue::new` refuse a library that reports another version (the structs are copied whole by the library).
-pub const AT2V_ABI_VERSION: c_int = 8;
+pub const AT2V_ABI_VERSION: c_int = 9;
 
 pub const AT2V_POLICY_DALEK_V1: c_int = 0;
 pub const AT2V_POLICY_LIBSODIUM_1_0_18: c_int = 1;
@@ -186,6 +186,10 @@ pub struct At2vInfo {
     pub experiments: u64,
     /// chunks staged by the host-buffer calls' pipeline
     pub host_chunks: u64,
+    /// pk/sig/msg bytes the host-buffer calls uploaded straight from caller memory (a `PinnedBuf`, a registered range)
+    pub host_direct_bytes: u64,
+    /// pk/sig/msg bytes that went through a staging slot
+    pub host_staged_bytes: u64,
 }
 
 /// `Default`: device 0, DALEK_V1, and the library defaults for every size (65536 records, 1 ms, 256 B, depth 3).
@@ -275,6 +279,10 @@ extern "C" {
     pub fn at2v_verify_batch_submit(ctx: *mut At2vCtx, pk: *const u8, sig: *const u8, msg: *const u8,
                                     msg_off: *const u32, n: usize, verdicts: *mut u32, ticket: *mut u64) -> c_int;
     pub fn at2v_verify_batch_wait(ctx: *mut At2vCtx, ticket: u64) -> c_int;
+    pub fn at2v_host_alloc(ctx: *mut At2vCtx, bytes: usize, out: *mut *mut c_void) -> c_int;
+    pub fn at2v_host_free(ctx: *mut At2vCtx, p: *mut c_void) -> c_int;
+    pub fn at2v_host_register(ctx: *mut At2vCtx, p: *mut c_void, bytes: usize) -> c_int;
+    pub fn at2v_host_unregister(ctx: *mut At2vCtx, p: *mut c_void) -> c_int;
     pub fn at2v_verify_batch_device(ctx: *mut At2vCtx, d_pk: *const u8, d_sig: *const u8, d_msg: *const u8,
                                     msg_bytes: usize, d_msg_off: *const u32, n: usize, d_verdicts: *mut u32,
                                     hip_stream: *mut c_void) -> c_int;
@@ -391,9 +399,18 @@ fn check_abi() -> Result<(), Error> {
     Ok(())
 }
 
+/// The context itself: destroyed when its verifier and every `PinnedBuf` allocated from it are gone.
+struct CtxHandle(*mut At2vCtx);
+
+impl Drop for CtxHandle {
+    fn drop(&mut self) {
+        unsafe { at2v_destroy(self.0) }
+    }
+}
+
 /// Owner of an at2v context (GPUs, or the CPU backend). Not Sync: one thread at a time; call from `spawn_blocking` or
 /// a dedicated thread, never on an async executor thread.
-pub struct BatchVerifier(*mut At2vCtx);
+pub struct BatchVerifier(*mut At2vCtx, std::sync::Arc<CtxHandle>);
 
 unsafe impl Send for BatchVerifier {}
 
@@ -402,7 +419,7 @@ impl BatchVerifier {
         check_abi()?;
         let mut p = std::ptr::null_mut();
         check(unsafe { at2v_create(opts, &mut p) })?;
-        Ok(BatchVerifier(p))
+        Ok(BatchVerifier(p, std::sync::Arc::new(CtxHandle(p))))
     }
 
     /// `num_gpus` devices from `device` on, library defaults otherwise.
@@ -477,11 +494,54 @@ impl BatchVerifier {
         check(unsafe { at2v_get_info(self.0, &mut i) })?;
         Ok(i)
     }
+
+    /// `bytes` of pinned memory the context knows (at2v_host_alloc; plain host memory on the CPU backend). Slices of it
+    /// passed to `verify` as pk / sig / msg are uploaded straight from there, without the copy into a staging slot that
+    /// pageable memory takes: receive payloads into a ring of these.
+    pub fn pinned(&mut self, bytes: usize) -> Result<PinnedBuf, Error> {
+        let mut p: *mut c_void = std::ptr::null_mut();
+        check(unsafe { at2v_host_alloc(self.0, bytes, &mut p) })?;
+        unsafe { std::ptr::write_bytes(p as *mut u8, 0, bytes) };
+        Ok(PinnedBuf { ctx: self.1.clone(), ptr: p as *mut u8, len: bytes })
+    }
 }
 
-impl Drop for BatchVerifier {
+/// Pinned host memory of a context (`BatchVerifier::pinned`): allocated on creation, zeroed, 64-byte aligned, freed on
+/// drop (at2v_host_free first completes the host-buffer calls in flight). It keeps the context alive, so it may outlive
+/// its verifier. Neither Send nor Sync: a context serves one thread at a time, and dropping a buffer is a call on the
+/// context; keep a verifier's buffers on the thread that uses the verifier.
+pub struct PinnedBuf {
+    ctx: std::sync::Arc<CtxHandle>,
+    ptr: *mut u8,
+    len: usize,
+}
+
+impl PinnedBuf {
+    pub fn len(&self) -> usize {
+        self.len
+    }
+
+    pub fn is_empty(&self) -> bool {
+        self.len == 0
+    }
+}
+
+impl std::ops::Deref for PinnedBuf {
+    type Target = [u8];
+    fn deref(&self) -> &[u8] {
+        unsafe { std::slice::from_raw_parts(self.ptr, self.len) }
+    }
+}
+
+impl std::ops::DerefMut for PinnedBuf {
+    fn deref_mut(&mut self) -> &mut [u8] {
+        unsafe { std::slice::from_raw_parts_mut(self.ptr, self.len) }
+    }
+}
+
+impl Drop for PinnedBuf {
     fn drop(&mut self) {
-        unsafe { at2v_destroy(self.0) }
+        unsafe { at2v_host_free(self.ctx.0, self.ptr as *mut c_void) };
     }
 }
 

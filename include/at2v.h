@@ -26,6 +26,8 @@ extern "C" {
 #endif
 
 /* ABI version of this header. Every struct passed by pointer is copied whole, so adding a field is an ABI break:
+ * version 9 added the pinned host memory calls (at2v_host_alloc / _free / _register / _unregister) and appended
+ * at2v_info.host_direct_bytes / host_staged_bytes;
  * version 8 added the reject reasons (at2v_reject_reasons / _device, at2v_verify_one_reason, at2v_reason_name,
  * at2v_queue_poll_reasons with the AT2V_QUEUE_REASONS queue flag; no struct changed);
  * version 7 appended at2v_info.experiments / host_chunks (and the AT2V_EXPERIMENT_* bits) and added
@@ -38,7 +40,7 @@ extern "C" {
  * at2v_opts.sender_comb and the AT2V_QUEUE_SENDER_COMB queue flag; version 3 appended at2v_opts.sender_cache, at2v_info.gathers / cache_* and the AT2V_E_PEER code (version 2 appended
  * at2v_opts.small_batch_max and at2v_queue_opts.flags). A binding checks at2v_abi_version() == AT2V_ABI_VERSION
  * before passing any struct (the Python and Rust bindings in this repo refuse a mismatching library). */
-#define AT2V_ABI_VERSION 8
+#define AT2V_ABI_VERSION 9
 int at2v_abi_version(void);
 
 typedef struct at2v_ctx at2v_ctx; /* opaque: device(s), streams, scratch, staging buffers, and the RCCL
@@ -84,7 +86,7 @@ typedef struct {
 #define AT2V_CTX_ADMIT_FIRST 2u
 /* With sender_comb: the throughput kernel's cached records take [s]B from a comb of B with 24-bit windows (11 positions,
  * 11.8 GB of HBM per device) instead of the default 20-bit one (13 positions, 872 MB): two table additions fewer per
- * record (37 instead of 39), +3% on repeating senders. Opt-in for its memory and its 0.75 s of table build at context
+ * record (37 instead of 39), +3% on repeating senders. Opt-in for its memory and its 26 ms of table build at context
  * creation; small-batch latency is unchanged with it. */
 #define AT2V_CTX_BCOMB_WIDE 4u
 #define AT2V_SMALL_BATCH_DEFAULT 32768u
@@ -149,6 +151,39 @@ int at2v_verify_batch(at2v_ctx* ctx, const uint8_t* pk, const uint8_t* sig, cons
 int at2v_verify_batch_submit(at2v_ctx* ctx, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg,
                              const uint32_t* msg_off, size_t n, uint32_t* verdicts, uint64_t* ticket);
 int at2v_verify_batch_wait(at2v_ctx* ctx, uint64_t ticket);
+
+/* ---- pinned host memory for the host-buffer calls ----
+ * at2v_verify_batch, at2v_verify_batch_submit / _wait and at2v_verify_batch_sharded copy pageable records into a pinned
+ * staging slot before the DMA engine can upload them. Records that already lie in pinned memory the context knows about
+ * skip that copy: their upload is submitted straight from the caller's memory. A node that receives payloads from the
+ * network receives them into such memory (a ring of at2v_host_alloc buffers). There is no new verify
+ * entry point; the calls above decide per array (pk, sig, msg) and per chunk of the call's upload schedule:
+ *   - an array's slice of a chunk goes direct when the bytes the chunk needs from it lie wholly inside ONE range that
+ *     this context allocated or registered; otherwise that slice is staged as before. Arrays of one call may mix (pk and
+ *     sig pinned, msg pageable), and a slice that straddles the end of a range is staged;
+ *   - the c + 1 message offsets of a chunk are always staged (they are rebased on the host) and counted in neither of
+ *     at2v_info.host_direct_bytes / host_staged_bytes;
+ *   - the verdict words may lie in a known range too; they are downloaded the same way wherever they lie;
+ *   - memory that is pinned but was not handed over through these calls (a hipHostMalloc of the caller's, a torch pinned
+ *     tensor) is unknown to the context and staged, exactly as before.
+ * at2v_host_alloc: `bytes` of pinned memory, 64-byte aligned, visible to every device of ctx, in *out.
+ * at2v_host_register: pins the caller's range [p, p + bytes) in place (any alignment; locked through the HSA runtime
+ * for every device of ctx) and makes it known to ctx; the
+ * caller keeps ownership and unregisters before freeing it. at2v_host_free / at2v_host_unregister take the pointer that
+ * at2v_host_alloc returned / at2v_host_register was given; both first complete the host-buffer calls in flight, as the
+ * synchronous call does (their results stay for their waits). at2v_destroy frees what is still allocated and unregisters
+ * what is still registered. A context is still not thread-safe: these calls are made by the thread that uses it.
+ * Errors: AT2V_E_INVALID for bytes == 0, a null out or p, a p that is not the start of a known range of the right kind
+ * (free: allocated, unregister: registered), a range that overlaps a known one, or a range the runtime does not report as
+ * pinned and reachable by every device of ctx (so that no upload is ever submitted from an address a device cannot read);
+ * AT2V_E_OOM when the allocation or the pin fails.
+ * A CPU context (num_gpus = 0) offers the same four calls and touches no device: at2v_host_alloc is a 64-byte-aligned
+ * host allocation, register / unregister only record the range, and both counters stay 0. A caller's code is the same on
+ * both backends. */
+int at2v_host_alloc(at2v_ctx* ctx, size_t bytes, void** out);
+int at2v_host_free(at2v_ctx* ctx, void* p);
+int at2v_host_register(at2v_ctx* ctx, void* p, size_t bytes);
+int at2v_host_unregister(at2v_ctx* ctx, void* p);
 
 /* Batch verify on device-resident buffers of ctx's first device (AT2V_E_NODEVICE on a CPU context), asynchronously on
  * `hip_stream`
@@ -271,6 +306,9 @@ typedef struct {
                                 record by its own sender's entry, whatever the other records of its chunk) */
   uint64_t experiments;      /* AT2V_EXPERIMENT_* bits compiled into this library (0 in a shipped build) */
   uint64_t host_chunks;      /* chunks staged by the host-buffer calls (at2v_verify_batch / _sharded pipeline) */
+  uint64_t host_direct_bytes; /* pk/sig/msg bytes the host-buffer calls uploaded straight from caller memory (a range
+                                 of at2v_host_alloc / at2v_host_register); all devices */
+  uint64_t host_staged_bytes; /* pk/sig/msg bytes that went through a staging slot */
 } at2v_info;
 /* With a sender cache, at2v_get_info first waits for the context's cache work (its build stream, which follows every
  * cached launch and therefore waits for those launches, and whatever each launch's stream ran before them). */

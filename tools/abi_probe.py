@@ -4,7 +4,12 @@ variants, for tuning the HostPipe staging (at2v_api.hip). Each variant sets the 
 AT2V_TEST_STAGE_MAX / AT2V_TEST_COPY_THREADS (AT2V_TEST_HOOKS=1) before creating its context; variants alternate over
 `--rounds` rounds so box drift hits them alike. Also prints the device-API kernel time of the same batch and a
 single-thread numpy copy rate of the batch (host memory bandwidth).
+--pinned: every variant is run twice per round, with the records in pageable numpy arrays and in memory of the context's
+at2v_host_alloc (uploaded straight from there, no staging copy); the two forms alternate within a round (pageable first
+in even rounds, pinned first in odd ones). Both are printed in ms per call and as a fraction of the device-API kernel
+time measured in this process; the JSON has the pinned form under "<variant>+pinned".
 usage: python tools/abi_probe.py [--n 1048576] [--calls 8] [--rounds 2] [--variants first:max:threads[:streams],...]
+       [--pinned] [--trace]
 -> one JSON line"""
 import argparse
 import json
@@ -23,6 +28,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--msg-len", type=int, default=100)
     ap.add_argument("--variants", default="32768:131072:8")
+    ap.add_argument("--pinned", action="store_true", help="also run every variant from at2v_host_alloc memory")
+    ap.add_argument("--trace", action="store_true", help="AT2V_TEST_PIPE_TRACE: the host's time per call, on stderr")
     ap.add_argument("--host-only", action="store_true", help="skip the device-API timings (for kernel traces)")
     ap.add_argument("--lib", default="", help="a libat2v variant (tools/build_variant.sh) instead of the product")
     a = ap.parse_args()
@@ -128,28 +135,48 @@ def main():
             os.environ["AT2V_TEST_STAGE_FIRST"] = first
             os.environ["AT2V_TEST_STAGE_MAX"] = mx
             os.environ["AT2V_TEST_COPY_THREADS"] = th
-            v = at2v.BatchVerifier()
-            lib = v._lib
-            ptrs = (pk.ctypes.data, sig.ctypes.data, msg.ctypes.data, off.ctypes.data)
-            assert lib.at2v_verify_batch(v._h, *ptrs, n, words.ctypes.data) == 0
-            times = []
-            for _ in range(a.calls):
-                t0 = time.perf_counter()
-                assert lib.at2v_verify_batch(v._h, *ptrs, n, words.ctypes.data) == 0
-                times.append((time.perf_counter() - t0) * 1e3)
-            ok = bool((words[: n // 32] == 0xFFFFFFFF).all())
-            chunks = v.info()["host_chunks"]
-            v.close()
-            d = out["variants"].setdefault(var, {"ms": [], "ok": True})
-            d["ms"].append(sorted(times)[len(times) // 2])
-            d["ok"] &= ok
-            d["chunks_per_call"] = chunks / (a.calls + 1)
-            print(f"[abi_probe] round {r} {var}: median {d['ms'][-1]:.3f} ms (min {min(times):.3f}) ok={ok}",
-                  file=sys.stderr, flush=True)
+            forms = ("pageable", "pinned") if a.pinned else ("pageable",)
+            for form in forms[::-1] if r % 2 else forms:
+                v = at2v.BatchVerifier()
+                lib = v._lib
+                if form == "pinned":  # the whole batch and its verdict words in one allocation of the context
+                    block = v.host_alloc(pk.nbytes + sig.nbytes + msg.nbytes + words.nbytes + 256)
+                    at, held = 0, []
+                    for src_arr in (pk, sig, msg, words):
+                        dst = block[at:at + src_arr.nbytes].view(src_arr.dtype)
+                        dst[:] = src_arr
+                        held.append(dst)
+                        at += (src_arr.nbytes + 63) // 64 * 64
+                    c_pk, c_sig, c_msg, c_words = held
+                else:
+                    c_pk, c_sig, c_msg, c_words = pk, sig, msg, words
+                c_words[:] = 0
+                ptrs = (c_pk.ctypes.data, c_sig.ctypes.data, c_msg.ctypes.data, off.ctypes.data)
+                print(f"[abi_probe] round {r} {var} {form}: {a.calls + 1} calls", file=sys.stderr, flush=True)
+                assert lib.at2v_verify_batch(v._h, *ptrs, n, c_words.ctypes.data) == 0
+                times = []
+                for _ in range(a.calls):
+                    t0 = time.perf_counter()
+                    assert lib.at2v_verify_batch(v._h, *ptrs, n, c_words.ctypes.data) == 0
+                    times.append((time.perf_counter() - t0) * 1e3)
+                ok = bool((c_words[: n // 32] == 0xFFFFFFFF).all())
+                inf = v.info()
+                v.close()
+                key = var if form == "pageable" else var + "+pinned"
+                d = out["variants"].setdefault(key, {"ms": [], "ok": True})
+                d["ms"].append(sorted(times)[len(times) // 2])
+                d["ok"] &= ok
+                d["chunks_per_call"] = inf["host_chunks"] / (a.calls + 1)
+                d["direct_bytes_per_call"] = inf["host_direct_bytes"] / (a.calls + 1)
+                d["staged_bytes_per_call"] = inf["host_staged_bytes"] / (a.calls + 1)
+                print(f"[abi_probe] round {r} {var} {form}: median {d['ms'][-1]:.3f} ms (min {min(times):.3f}, "
+                      f"{kernel_ms / d['ms'][-1]:.3f} of the device-API kernel) ok={ok}", file=sys.stderr, flush=True)
     for var, d in out["variants"].items():
         d["best_ms"] = min(d["ms"])
         d["rate_mps"] = n / d["best_ms"] / 1e3
         d["vs_kernel"] = kernel_ms / d["best_ms"]
+        d["median_ms"] = sorted(d["ms"])[len(d["ms"]) // 2]
+        d["spread_ms"] = max(d["ms"]) - min(d["ms"])  # round to round
     print(json.dumps(out))
 
 
