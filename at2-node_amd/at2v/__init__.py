@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = ("at2v_abi_version", "at2v_create", "at2v_destroy", "at2v_ver
                     "at2v_comm_get_unique_id", "at2v_comm_init_rank", "at2v_verify_shard_gather_device",
                     "at2v_verify_batch_sharded", "at2v_verify_batch_submit", "at2v_verify_batch_wait",
                     "at2v_host_alloc", "at2v_host_free", "at2v_host_register", "at2v_host_unregister",
+                    "at2v_sender_preload", "at2v_sender_unpin", "at2v_sender_query", "at2v_queue_sender_preload",
                     "at2v_queue_create", "at2v_queue_destroy", "at2v_queue_submit", "at2v_queue_flush",
                     "at2v_queue_poll", "at2v_queue_get_stats", "at2v_queue_reset_latency",
                     "at2v_pack_send_asset",
@@ -108,15 +109,30 @@ class _Info(ctypes.Structure):
 
 UNIQUE_ID_BYTES = 128  # AT2V_UNIQUE_ID_BYTES (RCCL ncclUniqueId)
 
+SENDER_PIN = 1      # include/at2v.h AT2V_SENDER_PIN: flag of at2v_sender_preload
+SENDER_CACHED = 1   # status bits of the known-senders calls, one byte per key: cached on every device of the context
+SENDER_PINNED = 2   # ... and no replacement pass evicts it
+SENDER_BAD_KEY = 4  # the 32 bytes do not decode under dalek's rules (records of such a key are rejected)
+
 
 _lib = None
+_loading = False
 
 
 def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     """Load libat2v.so (raises if it is missing: there is no fallback)."""
-    global _lib
+    global _lib, _loading
     if _lib is not None:
         return _lib
+    _loading = True
+    try:
+        _lib = _load(path)
+    finally:
+        _loading = False
+    return _lib
+
+
+def _load(path: str) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise At2vError(-2, f"{path} not built; run `make -C at2-node_amd` or __graft_entry__.build()")
     # One HIP runtime per process: torch bundles its own libamdhip64 (same SONAME as ROCm's). If torch is
@@ -131,6 +147,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.at2v_abi_version.restype = ctypes.c_int
     if lib.at2v_abi_version() != ABI_VERSION:  # the structs below would not match the library's
         raise At2vError(-1, f"{path} has ABI version {lib.at2v_abi_version()}, this binding needs {ABI_VERSION}")
+    # functions added within this ABI version (the known-senders calls): a library of the same version may predate them
+    for name in EXPORTED_SYMBOLS:
+        if not hasattr(lib, name):
+            raise At2vError(-1, f"{path} does not export {name}; rebuild it from this tree")
     P, u8p, u32p = ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32)
     lib.at2v_create.argtypes = [ctypes.POINTER(_Opts), ctypes.POINTER(P)]
     lib.at2v_create.restype = ctypes.c_int
@@ -150,6 +170,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.at2v_host_register.restype = ctypes.c_int
     lib.at2v_host_unregister.argtypes = [P, P]
     lib.at2v_host_unregister.restype = ctypes.c_int
+    lib.at2v_sender_preload.argtypes = [P, P, ctypes.c_size_t, ctypes.c_uint32, P]
+    lib.at2v_sender_preload.restype = ctypes.c_int
+    lib.at2v_sender_unpin.argtypes = [P, P, ctypes.c_size_t]
+    lib.at2v_sender_unpin.restype = ctypes.c_int
+    lib.at2v_sender_query.argtypes = [P, P, ctypes.c_size_t, P]
+    lib.at2v_sender_query.restype = ctypes.c_int
     lib.at2v_verify_batch_device.argtypes = [P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P, P]
     lib.at2v_verify_batch_device.restype = ctypes.c_int
     lib.at2v_verify_one.argtypes = [P, P, P, ctypes.c_size_t]
@@ -192,11 +218,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.at2v_reason_name.restype = ctypes.c_char_p
     from . import node as _node  # queue / packer / ledger signatures
     _node.bind(lib)
-    _lib = lib
     return lib
 
 
 def strerror(code: int) -> str:
+    if _loading:  # (an error raised while loading must not load again)
+        return "library not loaded"
     try:
         return load_library().at2v_strerror(code).decode()
     except At2vError:
@@ -347,6 +374,32 @@ class BatchVerifier:
         """at2v_host_unregister: `arr` starts at the first byte of a registered array"""
         _check(self._lib.at2v_host_unregister(self._h, arr.ctypes.data), "at2v_host_unregister")
         self._registered.pop(arr.ctypes.data, None)
+
+    # ---- known senders (include/at2v.h at2v_sender_*): tell the sender cache who will send, instead of waiting for it
+    # to learn keys from traffic
+    def sender_preload(self, pk: np.ndarray, pin: bool = False) -> np.ndarray:
+        """at2v_sender_preload: cache the listed keys (n x 32 bytes) on every device now, so the next launch serves their
+        records from the cache; pin: no replacement pass evicts them. Returns a status byte per key (SENDER_CACHED |
+        SENDER_PINNED | SENDER_BAD_KEY). At most sender_cache / 2 distinct keys per call, and as many pinned keys in
+        all. A context without a sender cache (or the CPU backend) caches nothing and reports only SENDER_BAD_KEY."""
+        pk = np.ascontiguousarray(pk, dtype=np.uint8).reshape(-1, 32)
+        status = np.zeros(max(1, len(pk)), np.uint8)
+        _check(self._lib.at2v_sender_preload(self._h, _ptr(pk) or None, len(pk), SENDER_PIN if pin else 0,
+                                             _ptr(status)), "at2v_sender_preload")
+        return status[:len(pk)]
+
+    def sender_unpin(self, pk: np.ndarray) -> None:
+        """at2v_sender_unpin: the listed keys lose their pin (unknown keys are ignored); their entries stay until the
+        replacement takes them"""
+        pk = np.ascontiguousarray(pk, dtype=np.uint8).reshape(-1, 32)
+        _check(self._lib.at2v_sender_unpin(self._h, _ptr(pk) or None, len(pk)), "at2v_sender_unpin")
+
+    def sender_query(self, pk: np.ndarray) -> np.ndarray:
+        """at2v_sender_query: a status byte per key, read-only (asking does not keep a key alive)"""
+        pk = np.ascontiguousarray(pk, dtype=np.uint8).reshape(-1, 32)
+        status = np.zeros(max(1, len(pk)), np.uint8)
+        _check(self._lib.at2v_sender_query(self._h, _ptr(pk) or None, len(pk), _ptr(status)), "at2v_sender_query")
+        return status[:len(pk)]
 
     @staticmethod
     def _verdict_words(n: int, words: Optional[np.ndarray]) -> np.ndarray:

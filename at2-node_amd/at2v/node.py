@@ -109,6 +109,7 @@ def bind(lib) -> None:
         "at2v_queue_poll": ([P, P, P, sz, u32], ctypes.c_long),
         "at2v_queue_poll_reasons": ([P, P, P, sz, u32], ctypes.c_long),
         "at2v_queue_get_stats": ([P, ctypes.POINTER(_QueueStats)], i32),
+        "at2v_queue_sender_preload": ([P, P, sz, u32, P], i32),
         "at2v_queue_reset_latency": ([P], i32),
         "at2v_pack_send_asset": ([P, sz, i32, P, P, P, P, P, P], ctypes.c_long),
         "at2v_ledger_create": ([ctypes.POINTER(P)], i32),
@@ -197,6 +198,18 @@ class IngestQueue:
 
     def flush(self) -> None:
         _chk(self._lib.at2v_queue_flush(self._h), "at2v_queue_flush")
+
+    def preload_senders(self, pk: np.ndarray, pin: bool = False) -> np.ndarray:
+        """at2v_queue_sender_preload: cache the listed senders' keys (n x 32 bytes) in the queue's context before their
+        traffic arrives, so their first payloads verify from the cache; pin: no replacement pass evicts them. Returns a
+        status byte per key (at2v.SENDER_CACHED | SENDER_PINNED | SENDER_BAD_KEY). Thread-safe, like submit and poll. A
+        queue on the CPU backend or without sender_comb caches nothing and reports only SENDER_BAD_KEY."""
+        from . import SENDER_PIN
+        pk = np.ascontiguousarray(pk, np.uint8).reshape(-1, 32)
+        status = np.zeros(max(1, len(pk)), np.uint8)
+        _chk(self._lib.at2v_queue_sender_preload(self._h, _p(pk), len(pk), SENDER_PIN if pin else 0, _p(status)),
+             "at2v_queue_sender_preload")
+        return status[:len(pk)]
 
     def poll(self, max_items: int = 65536, timeout_us: int = 0):
         """-> (tickets u64[k], verdicts u8[k]) in ticket order; a verdict is 1 (valid), 0 (invalid) or 0xff

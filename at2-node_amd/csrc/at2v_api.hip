@@ -21,6 +21,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -29,6 +30,7 @@
 #include <random>
 #include <mutex>
 #include <new>
+#include <set>
 #include <vector>
 
 #include "../../include/at2v.h"
@@ -79,6 +81,7 @@ struct SenderCache {
   DevBuf tags[2], entries[2];  // the live tag table / entries ([cur]) and the compaction target ([cur ^ 1])
   int cur = 0;
   DevBuf payload, free_slots, used, ctl, seen, claim_list[kClaimSlots];
+  DevBuf keys, key_status;  // a key list of at2v_sender_preload / _unpin / _query and its status bytes
   const int4* bcomb = nullptr;      // the combs of B, shared by the process's comb contexts on this device (bcomb_acquire)
   const int4* bcomb_lat = nullptr;
   // Builds run on the context's own stream (the shard's), which a caller's launches on its own streams never use: a
@@ -234,6 +237,9 @@ struct at2v_ctx {
   hipEvent_t gather_done = nullptr;  // recorded after every all-gather, on its stream (at2v_destroy waits for it)
   uint64_t gathers = 0;       // all-gathers issued (at2v_info.gathers)
   HostCall calls[3];          // host-buffer call slots (HostCall)
+  // at2v_sender_preload with AT2V_SENDER_PIN: the pinned keys, deduplicated here, so the capacity / 2 limit is exact and
+  // costs no device work (the entries' pin marks on the devices follow this set)
+  std::set<std::array<uint8_t, 32>> pinned;
   uint64_t next_ticket = 1;
 };
 
@@ -342,7 +348,7 @@ void free_cache(SenderCache*& c) {
   if (!c) return;
   if (c->build) (void)hipStreamSynchronize(c->build);  // (the shard's stream: destroyed with the shard)
   for (DevBuf* b : {&c->tags[0], &c->tags[1], &c->entries[0], &c->entries[1], &c->payload, &c->free_slots, &c->used,
-                    &c->ctl, &c->seen})
+                    &c->ctl, &c->seen, &c->keys, &c->key_status})
     b->release();
   bcomb_release(c->bcomb);
   bcomb_release(c->bcomb_lat);
@@ -435,6 +441,37 @@ int init_cache(Shard& s, uint32_t capacity, uint64_t seed, bool comb, bool admit
   return AT2V_OK;
 }
 
+// the counters' copy has landed (ctl_copied complete): what it says about compactions (thrash guard) and a full cache
+void cache_note_ctl_copy(SenderCache& c) {
+  c.copy_pending = false;
+  if (c.host_ctl[at2v::kCtlCompactions] > c.compactions_seen) {  // a compaction has run since the last look
+    c.compactions_seen = c.host_ctl[at2v::kCtlCompactions];
+    if (c.host_ctl[at2v::kCtlThreshold] == 0) {
+      c.freeze_len = c.freeze_len ? std::min<uint32_t>(2 * c.freeze_len, 256) : 8;
+      c.freeze_left = c.freeze_len;
+    } else {
+      c.freeze_len = 0;
+    }
+  }
+  if (c.host_ctl[at2v::kCtlFull] && !c.freeze_left) c.compact_pending = true;
+}
+
+// the build stream waits for every launch so far: the last one on each scratch set
+hipError_t wait_all_launches(Shard& s, hipStream_t st) {
+  hipError_t r = hipSuccess;
+  for (int k = 0; k < s.sets && r == hipSuccess; ++k) r = hipStreamWaitEvent(st, s.scratch_free[k], 0);
+  return r;
+}
+
+// a completed compaction's tables become the live ones
+void cache_swap_tables(SenderCache& c) {
+  const int nx = c.cur ^ 1;
+  c.cur = nx;
+  c.args.tags = (unsigned long long*)c.tags[nx].p;
+  c.args.entries = (int4*)c.entries[nx].p;
+  c.compacting = false;
+}
+
 // Before a cached launch on `stream`: wait until the launch's claim slot is free; if an earlier launch found the cache
 // full (its counters' copy has landed), enqueue a compaction on the build stream, behind every launch and build issued
 // so far. Launches issued while it runs look keys up in the old table and claim nothing (CacheArgs::no_claim), so they
@@ -444,38 +481,15 @@ int init_cache(Shard& s, uint32_t capacity, uint64_t seed, bool comb, bool admit
 // launches are done.
 hipError_t cache_before_launch(SenderCache& c, Shard& s, hipStream_t stream, int j) {
   hipError_t e = hipStreamWaitEvent(stream, c.slot_free[j], 0);
-  if (e == hipSuccess && c.copy_pending && hipEventQuery(c.ctl_copied) == hipSuccess) {
-    c.copy_pending = false;
-    if (c.host_ctl[at2v::kCtlCompactions] > c.compactions_seen) {  // a compaction has run since the last look
-      c.compactions_seen = c.host_ctl[at2v::kCtlCompactions];
-      if (c.host_ctl[at2v::kCtlThreshold] == 0) {
-        c.freeze_len = c.freeze_len ? std::min<uint32_t>(2 * c.freeze_len, 256) : 8;
-        c.freeze_left = c.freeze_len;
-      } else {
-        c.freeze_len = 0;
-      }
-    }
-    if (c.host_ctl[at2v::kCtlFull] && !c.freeze_left) c.compact_pending = true;
-  }
-  auto wait_all_launches = [&](hipStream_t st) {  // every launch so far: the last one on each scratch set
-    hipError_t r = hipSuccess;
-    for (int k = 0; k < s.sets && r == hipSuccess; ++k) r = hipStreamWaitEvent(st, s.scratch_free[k], 0);
-    return r;
-  };
+  if (e == hipSuccess && c.copy_pending && hipEventQuery(c.ctl_copied) == hipSuccess) cache_note_ctl_copy(c);
   if (e == hipSuccess && c.compacting && hipEventQuery(c.compacted) == hipSuccess) {
-    e = wait_all_launches(c.build);
-    if (e == hipSuccess) {
-      const int nx = c.cur ^ 1;
-      c.cur = nx;
-      c.args.tags = (unsigned long long*)c.tags[nx].p;
-      c.args.entries = (int4*)c.entries[nx].p;
-      c.compacting = false;
-    }
+    e = wait_all_launches(s, c.build);
+    if (e == hipSuccess) cache_swap_tables(c);
   }
   if (e == hipSuccess && c.compact_pending && !c.compacting) {
-    e = wait_all_launches(c.build);  // (the builds before it are on the build stream already)
+    e = wait_all_launches(s, c.build);  // (the builds before it are on the build stream already)
     const int nx = c.cur ^ 1;
-    at2v::CacheCompactArgs x{(unsigned long long*)c.tags[nx].p, (int4*)c.entries[nx].p, (uint32_t*)c.used.p};
+    at2v::CacheCompactArgs x{(unsigned long long*)c.tags[nx].p, (int4*)c.entries[nx].p, (uint32_t*)c.used.p, 0u};
     if (e == hipSuccess) e = at2v::launch_cache_compact(c.args, x, c.build);
     if (e == hipSuccess) e = hipEventRecord(c.compacted, c.build);
     if (e == hipSuccess) {
@@ -1477,6 +1491,248 @@ int at2v_host_unregister(at2v_ctx* ctx, void* p) {
   ctx->hostmem.remove(p);
   if (ctx->shards.empty()) return AT2V_OK;
   return hsa_amd_memory_unlock(p) == HSA_STATUS_SUCCESS ? AT2V_OK : AT2V_E_HIP;
+}
+
+// ---- known senders (at2v_sender_preload / _unpin / _query) ----
+// A CPU context, and a GPU context without a sender cache, only decode: every hip* call below is behind a shard's cache.
+
+namespace {
+
+using SenderKey = std::array<uint8_t, 32>;
+
+// the call's distinct keys in first-appearance order, and each listed key's index among them
+void distinct_keys(const uint8_t* pk, size_t n, std::vector<SenderKey>& keys, std::vector<uint32_t>& index) {
+  std::vector<std::pair<SenderKey, uint32_t>> order(n);
+  for (size_t i = 0; i < n; ++i) {
+    std::memcpy(order[i].first.data(), pk + 32 * i, 32);
+    order[i].second = (uint32_t)i;
+  }
+  std::sort(order.begin(), order.end());  // (equal keys: ascending index)
+  std::vector<uint32_t> first(n);         // per listed key: the index of its first appearance
+  for (size_t i = 0; i < n; ++i)
+    first[order[i].second] = i && order[i].first == order[i - 1].first ? first[order[i - 1].second] : order[i].second;
+  index.assign(n, 0);
+  keys.clear();
+  for (size_t i = 0; i < n; ++i) {
+    if (first[i] == i) {
+      index[i] = (uint32_t)keys.size();
+      SenderKey k;
+      std::memcpy(k.data(), pk + 32 * i, 32);
+      keys.push_back(k);
+    } else {
+      index[i] = index[first[i]];
+    }
+  }
+}
+
+// the shard's cache with no compaction under way: the build stream is behind every launch issued so far, and a
+// compaction that was enqueued has completed and its tables are the live ones (what cache_before_launch does once the
+// compaction's event has fired, here with a host wait: the calls that need it are synchronous)
+hipError_t cache_settle(SenderCache& c, Shard& s) {
+  hipError_t e = wait_all_launches(s, c.build);
+  if (e == hipSuccess && c.compacting) {
+    e = hipEventSynchronize(c.compacted);
+    if (e == hipSuccess) cache_swap_tables(c);
+  }
+  return e;
+}
+
+// the key list on the device (build stream), its status bytes behind it
+hipError_t upload_keys(SenderCache& c, const std::vector<SenderKey>& keys, at2v::CacheKeyList& l) {
+  hipError_t e = c.keys.ensure(keys.size() * 32);
+  if (e == hipSuccess) e = c.key_status.ensure(keys.size());
+  if (e == hipSuccess) e = hipMemcpyAsync(c.keys.p, keys.data(), keys.size() * 32, hipMemcpyHostToDevice, c.build);
+  l = at2v::CacheKeyList{(const uint8_t*)c.keys.p, (uint32_t)keys.size(), (uint8_t*)c.key_status.p};
+  return e;
+}
+
+// the list's status bytes as table `a` has them (build stream, then a host wait)
+hipError_t query_keys(SenderCache& c, const at2v::CacheArgs& a, const at2v::CacheKeyList& l, std::vector<uint8_t>& st) {
+  st.assign(l.n, 0);
+  hipError_t e = at2v::launch_cache_query(a, l, c.build);
+  if (e == hipSuccess) e = hipMemcpyAsync(st.data(), l.status, l.n, hipMemcpyDeviceToHost, c.build);
+  if (e == hipSuccess) e = hipStreamSynchronize(c.build);
+  return e;
+}
+
+// One shard's preload (current device = s.device): a launch-shaped step on the build stream. The keys go up; entries the
+// list already has are given the call's epoch, so a compaction that makes room keeps them; if the free list cannot hold
+// the new keys (or a compaction is due anyway) one compaction runs, with the room request, and is swapped in; then the
+// preload kernel claims into the call's claim slot, the usual builds and flip follow, and the statuses are read back.
+hipError_t preload_shard(SenderCache& c, Shard& s, const std::vector<SenderKey>& keys, bool pin,
+                         std::vector<uint8_t>& st) {
+  hipError_t e = cache_settle(c, s);
+  at2v::CacheKeyList l{};
+  if (e == hipSuccess) e = upload_keys(c, keys, l);
+  const int cs = (int)(c.launches % kClaimSlots);
+  if (e == hipSuccess) e = hipStreamWaitEvent(c.build, c.slot_free[cs], 0);
+  c.args.epoch = (uint32_t)++c.launches;  // entries the call creates or finds count as used by the latest launch
+  if (e == hipSuccess) e = at2v::launch_cache_pin(c.args, l, at2v::kPinTouch, c.build);
+  std::vector<unsigned long long> w((size_t)at2v::cache_ctl_words());
+  if (e == hipSuccess) e = hipMemcpyAsync(w.data(), c.ctl.p, w.size() * 8, hipMemcpyDeviceToHost, c.build);
+  if (e == hipSuccess) e = query_keys(c, c.args, l, st);  // (waits: every launch and build so far is done)
+  if (e != hipSuccess) return e;
+  if (c.copy_pending) cache_note_ctl_copy(c);  // (its copy is behind us on the build stream)
+  size_t fresh = 0;
+  for (uint8_t b : st) fresh += (b & AT2V_SENDER_CACHED) ? 0 : 1;
+  const unsigned long long fc = w[at2v::kCtlFreeCount], fh = std::min(w[at2v::kCtlFreeHead], fc);
+  if (fresh > fc - fh || c.compact_pending) {
+    const int nx = c.cur ^ 1;
+    at2v::CacheCompactArgs x{(unsigned long long*)c.tags[nx].p, (int4*)c.entries[nx].p, (uint32_t*)c.used.p,
+                             (uint32_t)fresh};
+    e = at2v::launch_cache_compact(c.args, x, c.build);
+    if (e == hipSuccess) e = hipEventRecord(c.compacted, c.build);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.build);
+    if (e != hipSuccess) return e;
+    cache_swap_tables(c);
+    c.compact_pending = false;
+    // the thrash guard judges compactions that traffic caused: this one was asked for (its cut may well be at age 0)
+    c.compactions_seen = w[at2v::kCtlCompactions] + 1;
+  }
+  at2v::CacheArgs ca = c.args;
+  ca.count_word = at2v::kCtlClaims0 + cs;
+  ca.new_list = (uint4*)c.claim_list[cs].p;
+  ca.admit_first = 1;  // an explicit request is not a sighting
+  ca.no_claim = 0;     // ... and no compaction is running: the freeze of the thrash guard does not apply either
+  e = at2v::launch_cache_preload(ca, l, pin ? at2v::kPinSet : at2v::kPinTouch, c.build);
+  if (e == hipSuccess) e = hipEventRecord(c.claims_ready[cs], c.build);
+  if (e == hipSuccess)
+    e = enqueue_cache_build(c, PendingBuild{ca, std::min<uint32_t>((uint32_t)keys.size(), ca.capacity), cs});
+  if (e == hipSuccess) e = hipEventSynchronize(c.built);
+  if (e == hipSuccess) e = query_keys(c, c.args, l, st);
+  return e;
+}
+
+int sender_args_check(at2v_ctx* ctx, const uint8_t* pk, size_t n) {
+  if (!ctx || (n && !pk) || n >= (1u << 31)) return AT2V_E_INVALID;
+  return AT2V_OK;
+}
+
+bool has_sender_cache(const at2v_ctx* ctx) { return !ctx->shards.empty() && ctx->shards[0].cache; }
+
+}  // namespace
+
+int at2v_sender_preload(at2v_ctx* ctx, const uint8_t* pk, size_t n, uint32_t flags, uint8_t* status) {
+  const int chk = sender_args_check(ctx, pk, n);
+  if (chk != AT2V_OK || (flags & ~AT2V_SENDER_PIN)) return AT2V_E_INVALID;
+  if (n == 0) return AT2V_OK;
+  try {
+    std::vector<uint8_t> bad(n);
+    at2v::cpu_sender_status(ctx->cpu, pk, n, bad.data());
+    if (!has_sender_cache(ctx)) {
+      if (status) std::memcpy(status, bad.data(), n);
+      return AT2V_OK;
+    }
+    const bool pin = (flags & AT2V_SENDER_PIN) != 0;
+    const size_t limit = ctx->shards[0].cache->args.capacity / 2;
+    std::vector<SenderKey> keys;
+    std::vector<uint32_t> index;
+    distinct_keys(pk, n, keys, index);
+    if (keys.size() > limit) return AT2V_E_INVALID;
+    if (pin) {
+      size_t add = 0;
+      for (const SenderKey& k : keys) add += ctx->pinned.count(k) ? 0 : 1;
+      if (ctx->pinned.size() + add > limit) return AT2V_E_INVALID;
+    }
+    quiesce_host_calls(ctx);
+    // (before the device work: the devices' pin marks are never ahead of this set, also when a shard fails below)
+    if (pin) ctx->pinned.insert(keys.begin(), keys.end());
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    std::vector<uint8_t> all(keys.size(), AT2V_SENDER_CACHED | AT2V_SENDER_PINNED), st;
+    hipError_t e = hipSuccess;
+    for (Shard& s : ctx->shards) {
+      if (e == hipSuccess) e = hipSetDevice(s.device);
+      if (e == hipSuccess) e = preload_shard(*s.cache, s, keys, pin, st);
+      if (e != hipSuccess) break;
+      for (size_t k = 0; k < keys.size(); ++k) all[k] &= st[k];
+    }
+    (void)hipSetDevice(prev);
+    if (e != hipSuccess) return hip_code(e);
+    for (size_t k = 0; k < keys.size(); ++k) {
+      if (!(all[k] & AT2V_SENDER_CACHED)) {  // not cached on every device: not cached, and no pin to count
+        all[k] = 0;
+        if (pin) ctx->pinned.erase(keys[k]);
+      }
+    }
+    if (status)
+      for (size_t i = 0; i < n; ++i) status[i] = (uint8_t)(bad[i] | all[index[i]]);
+    return AT2V_OK;
+  } catch (const std::bad_alloc&) {
+    return AT2V_E_OOM;
+  }
+}
+
+int at2v_sender_unpin(at2v_ctx* ctx, const uint8_t* pk, size_t n) {
+  const int chk = sender_args_check(ctx, pk, n);
+  if (chk != AT2V_OK || n == 0 || !has_sender_cache(ctx)) return chk;
+  try {
+    std::vector<SenderKey> keys;
+    std::vector<uint32_t> index;
+    distinct_keys(pk, n, keys, index);
+    for (const SenderKey& k : keys) ctx->pinned.erase(k);
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    hipError_t e = hipSuccess;
+    for (Shard& s : ctx->shards) {
+      SenderCache& c = *s.cache;
+      at2v::CacheKeyList l{};
+      if (e == hipSuccess) e = hipSetDevice(s.device);
+      if (e == hipSuccess) e = cache_settle(c, s);  // (a compaction under way copies the marks: clear them after it)
+      if (e == hipSuccess) e = upload_keys(c, keys, l);
+      if (e == hipSuccess) e = at2v::launch_cache_pin(c.args, l, at2v::kPinClear, c.build);
+      if (e == hipSuccess) e = hipStreamSynchronize(c.build);  // (the upload's source dies with this frame)
+    }
+    (void)hipSetDevice(prev);
+    return hip_code(e);
+  } catch (const std::bad_alloc&) {
+    return AT2V_E_OOM;
+  }
+}
+
+int at2v_sender_query(at2v_ctx* ctx, const uint8_t* pk, size_t n, uint8_t* status) {
+  const int chk = sender_args_check(ctx, pk, n);
+  if (chk != AT2V_OK || n == 0) return chk;
+  if (!status) return AT2V_E_INVALID;
+  try {
+    std::vector<uint8_t> bad(n);
+    at2v::cpu_sender_status(ctx->cpu, pk, n, bad.data());
+    std::memcpy(status, bad.data(), n);
+    if (!has_sender_cache(ctx)) return AT2V_OK;
+    std::vector<SenderKey> keys;
+    std::vector<uint32_t> index;
+    distinct_keys(pk, n, keys, index);
+    std::vector<uint8_t> all(keys.size(), AT2V_SENDER_CACHED | AT2V_SENDER_PINNED), st;
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    hipError_t e = hipSuccess;
+    for (Shard& s : ctx->shards) {
+      SenderCache& c = *s.cache;
+      at2v::CacheKeyList l{};
+      if (e == hipSuccess) e = hipSetDevice(s.device);
+      if (e == hipSuccess) e = upload_keys(c, keys, l);
+      // Reads only, and changes nothing of the cache's state on the host either: a compaction that is enqueued but not
+      // swapped in yet is ahead of the query on the build stream, so the query reads the tables it fills (what the next
+      // launch will swap in) without swapping them.
+      at2v::CacheArgs a = c.args;
+      if (c.compacting) {
+        a.tags = (unsigned long long*)c.tags[c.cur ^ 1].p;
+        a.entries = (int4*)c.entries[c.cur ^ 1].p;
+      }
+      if (e == hipSuccess) e = query_keys(c, a, l, st);
+      if (e != hipSuccess) break;
+      for (size_t k = 0; k < keys.size(); ++k) all[k] &= st[k];
+    }
+    (void)hipSetDevice(prev);
+    if (e != hipSuccess) return hip_code(e);
+    for (size_t i = 0; i < n; ++i) {
+      const uint8_t b = all[index[i]];
+      status[i] = (uint8_t)(bad[i] | ((b & AT2V_SENDER_CACHED) ? b : 0));
+    }
+    return AT2V_OK;
+  } catch (const std::bad_alloc&) {
+    return AT2V_E_OOM;
+  }
 }
 
 int at2v_verify_batch_device(at2v_ctx* ctx, const uint8_t* d_pk, const uint8_t* d_sig, const uint8_t* d_msg,

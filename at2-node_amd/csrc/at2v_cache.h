@@ -6,7 +6,8 @@
 //
 // Layout (round 4):
 //   tags[cap]      64-bit keyed fingerprints, 0 = free (open addressing, cap >= 2 x capacity: load <= 1/2)
-//   entries[cap]   4 granules: key (A's 32 bytes), meta = {decode verdict, valid, payload index u (-1: none), last epoch}
+//   entries[cap]   4 granules: key (A's 32 bytes), meta = {decode verdict, valid, payload index u (-1: none), last epoch},
+//                  mark = {pinned, 0, 0, 0} (at2v_sender_preload with AT2V_SENDER_PIN: no compaction evicts the entry)
 //   payload[u]     capacity payloads (a table [j]A or a comb), handed out from the free list free_slots[]
 // The verify kernels look their senders up themselves (chunk prologue) and claim new keys; a claim takes a payload
 // index from the free list and is listed in the launch's claim slot. After the launch the context's build stream builds
@@ -18,6 +19,9 @@
 // launch epoch, at most 3/4 of the capacity) move to the spare tag table with their payloads in place, every other
 // payload goes back to the free list, and a later launch swaps the tables once the compaction has completed. A key
 // claims a payload only at its second sighting (admission, CacheArgs::seen).
+// A caller that knows its senders does not wait for traffic (at2v_sender_preload): cache_preload_kernel
+// claims a key list exactly as a launch's lookups would (admission bypassed), the usual build and flip follow, and
+// cache_pin_kernel marks the entries pinned; a compaction keeps every pinned entry, then the most recently used ones.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -73,7 +77,17 @@ struct CacheCompactArgs {
   unsigned long long* new_tags;
   int4* new_entries;
   uint32_t* used;  // capacity flags: payload kept
+  uint32_t room;   // payloads a preload needs free afterwards (lowers the keep target; 0: a compaction from traffic)
 };
+
+// a key list on the device (at2v_sender_preload / _unpin / _query): n keys of 32 bytes, 16-byte aligned
+struct CacheKeyList {
+  const uint8_t* pk;
+  uint32_t n;
+  uint8_t* status;  // n bytes out (AT2V_SENDER_CACHED | AT2V_SENDER_PINNED), or nullptr
+};
+// what cache_pin_kernel does to the entries of a key list
+enum CachePinOp : int { kPinTouch = 0, kPinSet = 1, kPinClear = 2 };
 
 // ctl word indices the host reads (at2v_get_info) and resets
 enum CacheCtlWord : int {
@@ -98,7 +112,8 @@ enum CacheCtlWord : int {
   kCtlBuildTicks,    // wall-clock ticks of every build pass that built something (at2v_info.cache_build_us)
   kCtlBuilt,         // payloads built
   kCtlRecHits,       // records whose sender was served from the cache (partitioned launches)
-  kCtlHist,          // 64 age buckets
+  kCtlPinned,        // scratch word of a compaction: pinned entries that hold a payload (kept whatever their age)
+  kCtlHist,          // 64 age buckets of the unpinned entries
   kCtlWordsTotal = kCtlHist + 64
 };
 

@@ -35,6 +35,11 @@ void cpu_verify_batch(CpuPool* p, const uint8_t* pk, const uint8_t* sig, const u
 // bit i of valid_words = 1 iff pts[i] decodes under dalek rules (the kernels' gu_frombytes), synchronous
 void cpu_decode_points(CpuPool* p, const uint8_t* pts, size_t n, uint32_t* valid_words);
 
+// status[i] = AT2V_SENDER_BAD_KEY where pk[i] does not decode under dalek rules (gu_frombytes), else 0: what
+// at2v_sender_preload / _query report beside the cache bits, and all they report on a context without a sender cache.
+// Synchronous; p may be nullptr (a GPU context without a CPU pool: the calling thread decodes).
+void cpu_sender_status(CpuPool* p, const uint8_t* pk, size_t n, uint8_t* status);
+
 // reasons[i] = the at2v_reason of record i (at2v_reason.h reject_reason; 0 where bit i of verdict_words is set), n bytes,
 // synchronous. policy: AT2V_POLICY_*. Chunks of 64 records own their bytes.
 void cpu_reject_reasons(CpuPool* p, const uint8_t* pk, const uint8_t* sig, size_t n, const uint32_t* verdict_words,

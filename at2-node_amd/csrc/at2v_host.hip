@@ -396,6 +396,13 @@ long at2v_queue_poll_reasons(at2v_queue* q, uint64_t* tickets, uint8_t* reasons,
   return k < 0 ? AT2V_E_INVALID : k;
 }
 
+int at2v_queue_sender_preload(at2v_queue* q, const uint8_t* pk, size_t n, uint32_t flags, uint8_t* status) {
+  if (!q || !q->q) return AT2V_E_INVALID;
+  // the queue's context (a CPU context, or one without a sender cache, only decodes the keys); at2v_sender_preload sets
+  // and restores the calling thread's device itself
+  return q->q->between_launches([&] { return at2v_sender_preload(q->be.ctx, pk, n, flags, status); });
+}
+
 int at2v_queue_get_stats(at2v_queue* q, at2v_queue_stats* out) {
   if (!q || !q->q || !out) return AT2V_E_INVALID;
   const at2v::QueueStats s = q->q->stats();

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "at2v_cache.h"
+#include "at2v_cache_select.h"
 #include "at2v_comb.h"
 #include "at2v_kern_tables.h"
 
@@ -13,7 +14,8 @@ namespace at2v {
 
 // ---- per-sender A cache (at2v_opts.sender_cache; at2v_cache.h) ----
 // An entry (4 granules, one 64-byte line): key = the 32 bytes of A, meta = {dalek decode verdict of A, valid, payload
-// index u (-1: none), epoch of the last launch that used it}. A fingerprint only nominates an entry: a record takes it
+// index u (-1: none), epoch of the last launch that used it}, mark = {pinned, 0, 0, 0} (written by cache_pin_kernel
+// only: no lookup, claim or hit reads or writes the fourth granule). A fingerprint only nominates an entry: a record takes it
 // only if it is valid (its payload built and flipped by an earlier launch's build stream) and all 32 key bytes equal the
 // record's A, so a collision, a claim without a payload or an entry still being built costs speed, never a verdict.
 // Plain loads of an entry may be stale across XCDs inside one launch; every stale state (valid = 0, a zero key) only
@@ -416,33 +418,29 @@ __device__ AT2V_INLINE int entry_age(const CacheArgs& c, int4 m) {
   return a > 63u ? 63 : (int)a;
 }
 
-// compaction 1: age histogram of the entries that hold a payload (valid: every build has been flipped by now)
+__device__ AT2V_INLINE bool entry_pinned(const int4* ent) { return reinterpret_cast<const int*>(ent + 3)[0] == 1; }
+
+// compaction 1: the entries that hold a payload (valid: every build has been flipped by now): the pinned ones are
+// counted, the others go into the age histogram
 __global__ __launch_bounds__(256) void cache_hist_kernel(CacheArgs c) {
   for (uint32_t s = blockIdx.x * 256 + threadIdx.x; s < c.cap; s += gridDim.x * 256) {
     if (c.tags[s] == 0) continue;
-    const int4 m = c.entries[(size_t)s * kCacheEntryGranules + 2];
+    const int4* e = c.entries + (size_t)s * kCacheEntryGranules;
+    const int4 m = e[2];
     if (m.y != 1 || m.z < 0) continue;
-    atomicAdd(c.ctl + kCtlHist + entry_age(c, m), 1ull);
+    atomicAdd(c.ctl + (entry_pinned(e) ? kCtlPinned : kCtlHist + entry_age(c, m)), 1ull);
   }
 }
 
-// compaction 2 (one thread): keep every entry younger than T and `rem` of age T, at most 3/4 of the capacity, so a later
-// launch has a quarter of the payloads for new keys
-__global__ void cache_select_kernel(CacheArgs c) {
-  const unsigned long long target = (unsigned long long)c.capacity * 3 / 4;
-  unsigned long long kept = 0, rem = 0;
-  int T = 64;
-  for (int a = 0; a < 64; ++a) {
-    const unsigned long long h = c.ctl[kCtlHist + a];
-    if (kept + h > target) {
-      T = a;
-      rem = target - kept;
-      break;
-    }
-    kept += h;
-  }
-  c.ctl[kCtlThreshold] = (unsigned long long)T;
-  c.ctl[kCtlRemainder] = rem;
+// compaction 2 (one thread): keep every pinned entry, every other entry younger than T and `rem` of age T, at most 3/4
+// of the capacity (less when a preload asks for room), so a later launch has a quarter of the payloads for new keys
+// (cache_select, at2v_cache_select.h)
+__global__ void cache_select_kernel(CacheArgs c, CacheCompactArgs x) {
+  unsigned long long hist[64];
+  for (int a = 0; a < 64; ++a) hist[a] = c.ctl[kCtlHist + a];
+  const CacheSelection sel = cache_select(c.ctl[kCtlPinned], hist, c.capacity, x.room);
+  c.ctl[kCtlThreshold] = (unsigned long long)sel.threshold;
+  c.ctl[kCtlRemainder] = sel.rem;
   c.ctl[kCtlRemTaken] = 0;
   c.ctl[kCtlKept] = 0;
   c.ctl[kCtlFreeCount] = 0;
@@ -463,7 +461,8 @@ __global__ __launch_bounds__(256) void cache_compact_kernel(CacheArgs c, CacheCo
     const int4 m = e[2];
     if (m.y != 1 || m.z < 0) continue;  // a claim that never got a payload: its tag is dropped
     const int age = entry_age(c, m);
-    const bool keep = age < T || (age == T && atomicAdd(c.ctl + kCtlRemTaken, 1ull) < rem);
+    const bool pinned = entry_pinned(e);
+    const bool keep = pinned || age < T || (age == T && atomicAdd(c.ctl + kCtlRemTaken, 1ull) < rem);
     if (!keep) {
       atomicAdd(c.ctl + kCtlEvicted, 1ull);
       continue;
@@ -476,6 +475,7 @@ __global__ __launch_bounds__(256) void cache_compact_kernel(CacheArgs c, CacheCo
         d[0] = e[0];
         d[1] = e[1];
         d[2] = m;
+        d[3] = e[3];  // the pin mark
         x.used[m.z] = 1;
         atomicAdd(c.ctl + kCtlKept, 1ull);
         break;
@@ -488,6 +488,74 @@ __global__ __launch_bounds__(256) void cache_compact_kernel(CacheArgs c, CacheCo
 __global__ __launch_bounds__(256) void cache_freelist_kernel(CacheArgs c, CacheCompactArgs x) {
   for (uint32_t u = blockIdx.x * 256 + threadIdx.x; u < c.capacity; u += gridDim.x * 256)
     if (!x.used[u]) c.free_slots[atomicAdd(c.ctl + kCtlFreeCount, 1ull)] = u;
+}
+
+// ------------------------------------------------------------------ known senders (at2v_sender_preload / _unpin / _query)
+
+// The slot of A's entry, or -1: a probe along A's path that claims nothing, then all 32 key bytes compared (a fingerprint
+// shared with another key is no entry of A's). Called in a kernel of its own, after whatever wrote the keys.
+__device__ AT2V_INLINE int cache_probe(const CacheArgs& c, const uint32_t a[8]) {
+  const uint32_t mask = c.cap - 1;
+  const uint64_t fp = cache_fingerprint(a, c.seed, c.fp_mask);
+  const uint32_t h = (uint32_t)(fp >> 17) & mask;
+  for (uint32_t k = 0; k < 32; ++k) {
+    const uint32_t j = (h + k) & mask;
+    const unsigned long long t = __hip_atomic_load(c.tags + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t == 0) return -1;
+    if (t != fp) continue;
+    uint32_t key[8];
+    entry_key(key, c.entries + (size_t)j * kCacheEntryGranules);
+    bool same = true;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) same = same && key[i] == a[i];
+    return same ? (int)j : -1;  // (fingerprints are unique in a table)
+  }
+  return -1;
+}
+
+__device__ AT2V_INLINE uint8_t entry_status(const int4* ent) {
+  const int4 m = ent[2];
+  if (m.y != 1 || m.z < 0) return 0;
+  return (uint8_t)(1u | (entry_pinned(ent) ? 2u : 0u));  // AT2V_SENDER_CACHED | AT2V_SENDER_PINNED
+}
+
+// Preload 1 (build stream, no launch in flight): one key per lane, looked up exactly as a launch's records are
+// (cache_lookup_wave; the context passes admit_first = 1, no_claim = 0, the call's claim slot and epoch), so a new key
+// claims a tag and a payload and lands in the claim list for cache_build_kernel / cache_comb_kernel and the flip.
+// Duplicates within a wave elect one leader, duplicates across waves meet in the tag CAS.
+__global__ __launch_bounds__(256) void cache_preload_kernel(CacheArgs c, CacheKeyList l) {
+  const int lane = threadIdx.x & 63;
+  for (uint32_t w0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; w0 < l.n; w0 += gridDim.x * 256) {  // wave-uniform
+    const uint32_t i = w0 + (uint32_t)lane;
+    const bool active = i < l.n;
+    uint32_t Aw[8];
+    load8(Aw, l.pk + (size_t)(active ? i : l.n - 1) * 32);
+    (void)cache_lookup_wave(c, Aw, lane, active);
+  }
+}
+
+// Preload 2 / unpin (a kernel of its own: every key the claims above wrote is visible): the entry of each listed key
+// gets the call's epoch (kPinTouch, kPinSet: the compaction treats it as just used) and its pin mark set or cleared.
+__global__ __launch_bounds__(256) void cache_pin_kernel(CacheArgs c, CacheKeyList l, int op) {
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < l.n; i += gridDim.x * 256) {
+    uint32_t Aw[8];
+    load8(Aw, l.pk + (size_t)i * 32);
+    const int slot = cache_probe(c, Aw);
+    if (slot < 0) continue;
+    int4* e = c.entries + (size_t)slot * kCacheEntryGranules;
+    if (op != kPinClear) reinterpret_cast<int*>(e + 2)[3] = (int)c.epoch;
+    if (op != kPinTouch) reinterpret_cast<int*>(e + 3)[0] = op == kPinSet ? 1 : 0;
+  }
+}
+
+// Query: status bits per listed key; reads only (no claim, no epoch, no counter, no kCtlFull).
+__global__ __launch_bounds__(256) void cache_query_kernel(CacheArgs c, CacheKeyList l) {
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < l.n; i += gridDim.x * 256) {
+    uint32_t Aw[8];
+    load8(Aw, l.pk + (size_t)i * 32);
+    const int slot = cache_probe(c, Aw);
+    l.status[i] = slot < 0 ? (uint8_t)0 : entry_status(c.entries + (size_t)slot * kCacheEntryGranules);
+  }
 }
 
 }  // namespace at2v

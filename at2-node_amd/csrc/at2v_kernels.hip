@@ -378,13 +378,34 @@ hipError_t launch_cache_compact(const CacheArgs& c, const CacheCompactArgs& x, h
   hipError_t e = hipMemsetAsync(x.new_tags, 0, (size_t)c.cap * 8, stream);
   if (e == hipSuccess) e = hipMemsetAsync(x.new_entries, 0, (size_t)c.cap * kCacheEntryGranules * 16, stream);
   if (e == hipSuccess) e = hipMemsetAsync(x.used, 0, (size_t)c.capacity * 4, stream);
-  if (e == hipSuccess) e = hipMemsetAsync(c.ctl + kCtlHist, 0, 64 * 8, stream);
+  static_assert(kCtlHist == kCtlPinned + 1, "the pinned count and the histogram are zeroed as one span");
+  if (e == hipSuccess) e = hipMemsetAsync(c.ctl + kCtlPinned, 0, 65 * 8, stream);
   if (e != hipSuccess) return e;
   const uint32_t gs = grid_for(c.cap, 256, 2048), gu = grid_for(c.capacity, 256, 2048);
   hipLaunchKernelGGL(cache_hist_kernel, dim3(gs), dim3(256), 0, stream, c);
-  hipLaunchKernelGGL(cache_select_kernel, dim3(1), dim3(1), 0, stream, c);
+  hipLaunchKernelGGL(cache_select_kernel, dim3(1), dim3(1), 0, stream, c, x);
   hipLaunchKernelGGL(cache_compact_kernel, dim3(gs), dim3(256), 0, stream, c, x);
   hipLaunchKernelGGL(cache_freelist_kernel, dim3(gu), dim3(256), 0, stream, c, x);
+  return hipGetLastError();
+}
+
+hipError_t launch_cache_preload(const CacheArgs& c, const CacheKeyList& l, int pin_op, hipStream_t stream) {
+  if (l.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(cache_preload_kernel, dim3(grid_for(l.n, 256, 1024)), dim3(256), 0, stream, c, l);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return launch_cache_pin(c, l, pin_op, stream);
+}
+
+hipError_t launch_cache_pin(const CacheArgs& c, const CacheKeyList& l, int pin_op, hipStream_t stream) {
+  if (l.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(cache_pin_kernel, dim3(grid_for(l.n, 256, 1024)), dim3(256), 0, stream, c, l, pin_op);
+  return hipGetLastError();
+}
+
+hipError_t launch_cache_query(const CacheArgs& c, const CacheKeyList& l, hipStream_t stream) {
+  if (l.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(cache_query_kernel, dim3(grid_for(l.n, 256, 1024)), dim3(256), 0, stream, c, l);
   return hipGetLastError();
 }
 

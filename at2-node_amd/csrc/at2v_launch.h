@@ -56,5 +56,11 @@ hipError_t launch_cache_init(const CacheArgs& c, hipStream_t stream);
 hipError_t launch_cache_build(const CacheArgs& c, uint32_t max_claims, hipStream_t stream);
 // compact a full cache into (x.new_tags, x.new_entries) (stream order; no cached launch or build may be in flight)
 hipError_t launch_cache_compact(const CacheArgs& c, const CacheCompactArgs& x, hipStream_t stream);
+// Known senders (at2v_sender_preload / _unpin / _query; stream order, no cached launch in flight). Preload: claim the
+// listed keys into claim slot c (admission bypassed: the caller sets c.admit_first), then give their entries c.epoch and
+// apply pin_op (CachePinOp); launch_cache_build follows. Pin: the second step alone. Query: l.status per key, reads only.
+hipError_t launch_cache_preload(const CacheArgs& c, const CacheKeyList& l, int pin_op, hipStream_t stream);
+hipError_t launch_cache_pin(const CacheArgs& c, const CacheKeyList& l, int pin_op, hipStream_t stream);
+hipError_t launch_cache_query(const CacheArgs& c, const CacheKeyList& l, hipStream_t stream);
 
 }  // namespace at2v

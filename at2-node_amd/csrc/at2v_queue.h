@@ -224,6 +224,14 @@ class BatchQueue {
     return (long)k;
   }
 
+  // Run f() between two launches, from any thread: under launch_m_, the lock every launch runs under, so f may use
+  // what the backend's launch() uses (a context that is not thread-safe). Batches sealed meanwhile wait for the launcher.
+  template <class F>
+  int between_launches(F&& f) {
+    std::lock_guard<std::mutex> g(launch_m_);
+    return f();
+  }
+
   QueueStats stats() {
     std::lock_guard<std::mutex> lk(m_);
     QueueStats s = stats_;

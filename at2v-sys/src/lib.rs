@@ -77,6 +77,12 @@ pub const AT2V_REASON_R_ENCODING: u8 = 5;
 pub const AT2V_REASON_EQUATION: u8 = 6;
 pub const AT2V_REASON_UNKNOWN: u8 = 255;
 
+/// include/at2v.h: the flag of at2v_sender_preload and the status bits of the known-senders calls (one byte per key)
+pub const AT2V_SENDER_PIN: u32 = 1;
+pub const AT2V_SENDER_CACHED: u8 = 1;
+pub const AT2V_SENDER_PINNED: u8 = 2;
+pub const AT2V_SENDER_BAD_KEY: u8 = 4;
+
 /// Why a record was rejected (at2v_reason, the header's values). `ADecode` is what the reference answers with
 /// InvalidArgument at ingest (rpc.rs:240-243, :265-269); `SRange`..`Equation` are a payload that is never delivered.
 #[repr(u8)]
@@ -283,6 +289,10 @@ extern "C" {
     pub fn at2v_host_free(ctx: *mut At2vCtx, p: *mut c_void) -> c_int;
     pub fn at2v_host_register(ctx: *mut At2vCtx, p: *mut c_void, bytes: usize) -> c_int;
     pub fn at2v_host_unregister(ctx: *mut At2vCtx, p: *mut c_void) -> c_int;
+    // added within ABI version 9 (no struct changed): a library that predates them fails at link time
+    pub fn at2v_sender_preload(ctx: *mut At2vCtx, pk: *const u8, n: usize, flags: u32, status: *mut u8) -> c_int;
+    pub fn at2v_sender_unpin(ctx: *mut At2vCtx, pk: *const u8, n: usize) -> c_int;
+    pub fn at2v_sender_query(ctx: *mut At2vCtx, pk: *const u8, n: usize, status: *mut u8) -> c_int;
     pub fn at2v_verify_batch_device(ctx: *mut At2vCtx, d_pk: *const u8, d_sig: *const u8, d_msg: *const u8,
                                     msg_bytes: usize, d_msg_off: *const u32, n: usize, d_verdicts: *mut u32,
                                     hip_stream: *mut c_void) -> c_int;
@@ -326,6 +336,7 @@ extern "C" {
                            -> c_long;
     pub fn at2v_queue_poll_reasons(q: *mut At2vQueue, tickets: *mut u64, reasons: *mut u8, max: usize, timeout_us: u32)
                                    -> c_long;
+    pub fn at2v_queue_sender_preload(q: *mut At2vQueue, pk: *const u8, n: usize, flags: u32, status: *mut u8) -> c_int;
     pub fn at2v_queue_get_stats(q: *mut At2vQueue, out: *mut At2vQueueStats) -> c_int;
     pub fn at2v_queue_reset_latency(q: *mut At2vQueue) -> c_int;
 
@@ -489,6 +500,36 @@ impl BatchVerifier {
         Ok(bytes.into_iter().map(RejectReason::from_byte).collect())
     }
 
+    /// Known senders (at2v_sender_preload): cache the listed 32-byte keys on every device now, so the next launch serves
+    /// their records from the sender cache instead of waiting for the cache to learn them from traffic; `pin`: no
+    /// replacement pass evicts them. One status byte per key (AT2V_SENDER_CACHED | _PINNED | _BAD_KEY). At most
+    /// sender_cache / 2 distinct keys per call and as many pinned keys in all (Err(AT2V_E_INVALID), nothing changes).
+    /// Without a sender cache, and on the CPU backend, nothing is cached and only _BAD_KEY is reported.
+    pub fn preload_senders(&mut self, keys: &[[u8; 32]], pin: bool) -> Result<Vec<u8>, Error> {
+        let mut status = vec![0u8; keys.len()];
+        let flags = if pin { AT2V_SENDER_PIN } else { 0 };
+        check(unsafe {
+            at2v_sender_preload(self.0, keys.as_ptr() as *const u8, keys.len(), flags, status.as_mut_ptr())
+        })?;
+        Ok(status)
+    }
+
+    /// at2v_sender_unpin: the listed keys lose their pin (unknown keys are ignored); their entries stay cached until the
+    /// replacement takes them.
+    pub fn unpin_senders(&mut self, keys: &[[u8; 32]]) -> Result<(), Error> {
+        check(unsafe { at2v_sender_unpin(self.0, keys.as_ptr() as *const u8, keys.len()) }).map(|_| ())
+    }
+
+    /// at2v_sender_query: one status byte per key, read-only (asking does not keep a key alive).
+    pub fn query_senders(&mut self, keys: &[[u8; 32]]) -> Result<Vec<u8>, Error> {
+        let mut status = vec![0u8; keys.len()];
+        if keys.is_empty() {
+            return Ok(status);
+        }
+        check(unsafe { at2v_sender_query(self.0, keys.as_ptr() as *const u8, keys.len(), status.as_mut_ptr()) })?;
+        Ok(status)
+    }
+
     pub fn info(&self) -> Result<At2vInfo, Error> {
         let mut i = At2vInfo::default();
         check(unsafe { at2v_get_info(self.0, &mut i) })?;
@@ -601,6 +642,17 @@ impl Queue {
             return Err(Error(k as c_int));
         }
         Ok((0..k as usize).map(|i| (t[i], RejectReason::from_byte(r[i]))).collect())
+    }
+
+    /// at2v_queue_sender_preload: `BatchVerifier::preload_senders` on the queue's own context, from any thread (it runs
+    /// between two of the queue's launches). A queue on the CPU backend or without AT2V_QUEUE_SENDER_COMB caches nothing.
+    pub fn preload_senders(&self, keys: &[[u8; 32]], pin: bool) -> Result<Vec<u8>, Error> {
+        let mut status = vec![0u8; keys.len()];
+        let flags = if pin { AT2V_SENDER_PIN } else { 0 };
+        check(unsafe {
+            at2v_queue_sender_preload(self.0, keys.as_ptr() as *const u8, keys.len(), flags, status.as_mut_ptr())
+        })?;
+        Ok(status)
     }
 
     pub fn stats(&self) -> Result<At2vQueueStats, Error> {

@@ -27,7 +27,9 @@ extern "C" {
 
 /* ABI version of this header. Every struct passed by pointer is copied whole, so adding a field is an ABI break:
  * version 9 added the pinned host memory calls (at2v_host_alloc / _free / _register / _unregister) and appended
- * at2v_info.host_direct_bytes / host_staged_bytes;
+ * at2v_info.host_direct_bytes / host_staged_bytes; the known-senders calls (at2v_sender_preload / _unpin / _query,
+ * at2v_queue_sender_preload) were added within version 9: they touch no struct, so the number did not move, and a
+ * binding that needs them checks that the library exports them;
  * version 8 added the reject reasons (at2v_reject_reasons / _device, at2v_verify_one_reason, at2v_reason_name,
  * at2v_queue_poll_reasons with the AT2V_QUEUE_REASONS queue flag; no struct changed);
  * version 7 appended at2v_info.experiments / host_chunks (and the AT2V_EXPERIMENT_* bits) and added
@@ -184,6 +186,47 @@ int at2v_host_alloc(at2v_ctx* ctx, size_t bytes, void** out);
 int at2v_host_free(at2v_ctx* ctx, void* p);
 int at2v_host_register(at2v_ctx* ctx, void* p, size_t bytes);
 int at2v_host_unregister(at2v_ctx* ctx, void* p);
+
+/* ---- known senders: preload, pin and query the sender cache (added within ABI version 9: no struct changed) ----
+ * The sender cache (at2v_opts.sender_cache) learns keys from traffic: a key is usable only after it was seen twice and
+ * its payload was built behind a launch, and the least recently used keys make room for new ones. A node that knows who
+ * will send (its peers, its accounts after a restart) says so with these calls instead.
+ * pk: n x 32 bytes (duplicates allowed, they count once); status: n bytes out, one per key, an OR of
+ *   AT2V_SENDER_CACHED   a valid entry with a built payload, on every device of the context
+ *   AT2V_SENDER_PINNED   ... that no replacement pass evicts
+ *   AT2V_SENDER_BAD_KEY  the 32 bytes do not decode under dalek's rules (V2); such a key is cached like any other, with
+ *                        decode verdict 0, and its records are rejected from the cache
+ * at2v_sender_preload is synchronous. On AT2V_OK every listed key that could be cached has a built payload (a [j]A
+ * table, or a comb with sender_comb) on EVERY device of the context (shards split a batch by index, so any sender may
+ * land on any device), and the very next verify launch, on any stream, serves its records from the cache: the
+ * throughput kernels, the partitioned launch and the small-batch comb kernel alike. The call is ordered against what is
+ * already enqueued: it completes the host-buffer calls in flight (as at2v_host_free does), its device work waits for the
+ * last launch on each scratch set, and a replacement pass that is pending or not yet swapped in is finished first. It
+ * bypasses the admission filter and the thrash-guard freeze (an explicit request is not a sighting), and the entries it
+ * creates or finds count as used by the latest launch. flags: AT2V_SENDER_PIN pins the listed keys: replacement passes
+ * keep pinned entries first, then the most recently used ones. Room is made inside the call: if the free payloads cannot
+ * hold the new keys, one replacement pass runs first, keeping min(3/4 capacity, capacity - keys to add) entries.
+ * Limits, both AT2V_E_INVALID and nothing changes: more than capacity / 2 distinct keys in one call; a pinning call that
+ * would take the number of pinned keys above capacity / 2 (capacity: at2v_opts.sender_cache, per device). Also
+ * AT2V_E_INVALID: unknown flag bits, a NULL pk with n > 0, (query) a NULL status with n > 0. n = 0 is AT2V_OK; status
+ * may be NULL for preload.
+ * A key that cannot get an entry (its fingerprint collides with another key's, or its probe path is full) is simply not
+ * cached: its status has neither CACHED nor PINNED, it is not counted as pinned, the call still returns AT2V_OK, and
+ * its records verify without the cache as before. Speed changes, a verdict never does.
+ * at2v_sender_unpin clears the pin of the listed keys (unknown keys are ignored); the entries stay until the
+ * replacement takes them. at2v_sender_query is read-only: it claims nothing and refreshes no entry, so asking does not
+ * keep a key alive; CACHED means cached on every device.
+ * A GPU context with sender_cache = 0 and a CPU context (num_gpus = 0, no HIP call) offer the same calls: nothing is
+ * cached, every status has only the BAD_KEY bit (the CPU decode), the return is AT2V_OK. A caller's code is the same on
+ * both backends. Errors otherwise as elsewhere (AT2V_E_HIP, AT2V_E_OOM); after a failed preload the context keeps
+ * working and nothing half-built is ever valid. As every context call: one thread at a time. */
+#define AT2V_SENDER_PIN 1u     /* flag of at2v_sender_preload */
+#define AT2V_SENDER_CACHED 1u  /* status bits, one byte per key */
+#define AT2V_SENDER_PINNED 2u
+#define AT2V_SENDER_BAD_KEY 4u
+int at2v_sender_preload(at2v_ctx* ctx, const uint8_t* pk, size_t n, uint32_t flags, uint8_t* status);
+int at2v_sender_unpin(at2v_ctx* ctx, const uint8_t* pk, size_t n);
+int at2v_sender_query(at2v_ctx* ctx, const uint8_t* pk, size_t n, uint8_t* status);
 
 /* Batch verify on device-resident buffers of ctx's first device (AT2V_E_NODEVICE on a CPU context), asynchronously on
  * `hip_stream`
@@ -398,6 +441,11 @@ long at2v_queue_poll(at2v_queue* q, uint64_t* tickets, uint8_t* verdicts, size_t
 /* The same, with an at2v_reason byte per ticket instead of the verdict (0 = valid, 1..6 = why it was rejected, 0xff =
  * the batch failed). A queue created without AT2V_QUEUE_REASONS returns AT2V_E_INVALID. */
 long at2v_queue_poll_reasons(at2v_queue* q, uint64_t* tickets, uint8_t* reasons, size_t max, uint32_t timeout_us);
+/* at2v_sender_preload on the queue's own context (same arguments, limits and status bytes). Thread-safe like the rest
+ * of the queue: it serialises with the queue's launches, so it runs between two batches, and the next batch launched
+ * finds the keys cached. A queue on the CPU backend, or one without AT2V_QUEUE_SENDER_COMB, behaves as a context without
+ * a sender cache: AT2V_OK, every status only the BAD_KEY bit. */
+int at2v_queue_sender_preload(at2v_queue* q, const uint8_t* pk, size_t n, uint32_t flags, uint8_t* status);
 int at2v_queue_get_stats(at2v_queue* q, at2v_queue_stats* out);
 int at2v_queue_reset_latency(at2v_queue* q);
 

@@ -15,6 +15,9 @@ For batches of B records (default 1, 20, 64, 1024), each measured `--reps` times
              own stream: `first_combs_ready_us` is the wall time from the launch until at2v_get_info returns;
              `first_launch_shared_hw_queue_us` is a launch of 64 new keys on a stream that shares a hardware queue
              with the context's stream (its end waits for the builds);
+             `first_launch_preloaded_keys_us` is the first launch of B more new keys that at2v_sender_preload was given
+             beforehand (they are served from the cache: the line to read beside `warm_launches_new_keys_us` and
+             `first_launch_new_keys_us`), `preload_call_us` the wall time of that preload call;
 reports p50/p90 per stage as JSON. Records come from the oracle generator (all valid), checked once per size."""
 import argparse
 import json
@@ -74,7 +77,7 @@ def main():
             # build.
             ls, _, _, sh = at2v.launch_streams(4)
             # a running node's context: two earlier launches (other keys) before the measured one
-            wp, wg, wm, wf = o.gen_records(0x4154325F, 1 << 30, 3 * 64 + B, a.msg_len)
+            wp, wg, wm, wf = o.gen_records(0x4154325F, 1 << 30, 3 * 64 + 2 * B, a.msg_len)
             wd = [torch.from_numpy(x.reshape(-1).copy()).cuda() for x in (wp, wg)]
             wdm = torch.from_numpy(np.concatenate([wm, np.zeros(16, np.uint8)])).cuda()
             wv = torch.zeros((B + 31) // 32 + 2, dtype=torch.int32, device="cuda")
@@ -100,6 +103,16 @@ def main():
             warm = [launch_new(0, 64, ls)[0], launch_new(64, 64, ls)[0]]
             first_us, combs_ready_us = launch_new(128, B, ls)
             shared_us, _ = launch_new(128 + B, 64, sh)
+            # known senders: B more new keys, preloaded (at most half the cache per call), then their first launch
+            lo = 192 + B
+            t = time.perf_counter()
+            for k in range(0, B, 512):
+                st = vc.sender_preload(wp[lo + k:lo + min(B, k + 512)])
+                assert (st == at2v.SENDER_CACHED).all()
+            preload_us = (time.perf_counter() - t) * 1e6
+            h0 = vc.info()["cache_chunk_hits"]
+            preloaded_us, _ = launch_new(lo, B, ls)
+            assert vc.info()["cache_chunk_hits"] - h0 == (B + 63) // 64  # served from the cache
             vc.close()
         fresh = []
         if a.comb and a.fresh_reps:
@@ -150,6 +163,8 @@ def main():
             out["sizes"][B]["first_combs_ready_us"] = combs_ready_us
             out["sizes"][B]["warm_launches_new_keys_us"] = warm
             out["sizes"][B]["first_launch_shared_hw_queue_us"] = shared_us
+            out["sizes"][B]["first_launch_preloaded_keys_us"] = preloaded_us
+            out["sizes"][B]["preload_call_us"] = preload_us
         print(B, json.dumps(out["sizes"][B]), file=sys.stderr)
     q.close()
     v.close()

@@ -39,6 +39,14 @@ def node_main(idx, inboxes, result_q, args, total, node_ready=None):
 
     q = IngestQueue(device=0, max_batch=args.batch, max_delay_us=args.delay_us, max_msg_bytes=48, depth=3,
                     eager=args.eager, sender_comb=bool(args.comb), sender_cache=args.cache)
+    preloaded = 0
+    if args.preload_senders and args.comb:
+        # known senders (at2v_queue_sender_preload): the client's keys, regular senders first, as many as the cache holds,
+        # at most half the cache per call; their first payloads then verify from the cache instead of the slow path
+        cap = args.cache or 1024
+        keys = np.frombuffer(b"".join(KEYS[:cap]), np.uint8).reshape(-1, 32)
+        for k in range(0, len(keys), max(1, cap // 2)):
+            preloaded += int((q.preload_senders(keys[k:k + cap // 2]) & 1).sum())
     if node_ready is not None:  # the context (and its tables) is built: traffic may start
         node_ready.put(idx)
     led = Ledger()
@@ -140,7 +148,7 @@ def node_main(idx, inboxes, result_q, args, total, node_ready=None):
     result_q.put({"node": idx, **stats, "pending": led.pending(), "ledger_sha256": h.hexdigest(),
                   "lat_p50_us": float(np.percentile(lat_us, 50)), "lat_p99_us": float(np.percentile(lat_us, 99)),
                   "queue_p50_us": qs["p50_us"], "queue_p99_us": qs["p99_us"], "queue_batches": qs["batches"],
-                  "queue_mean_batch": qs["mean_batch"]})
+                  "queue_mean_batch": qs["mean_batch"], "preloaded_keys": preloaded})
 
 
 def senders(args):
@@ -277,6 +285,8 @@ def main():
     ap.add_argument("--fresh-frac", type=float, default=0.0,
                     help="extra transfers from first-seen senders, as a fraction of the regular traffic (one each)")
     ap.add_argument("--cache", type=int, default=0, help="keys per node queue context with --comb (0 = 1024)")
+    ap.add_argument("--preload-senders", type=int, default=0,
+                    help="1 = with --comb, each node preloads the client's keys into its sender cache before traffic starts")
     ap.add_argument("--bad-frac", type=float, default=0.02)
     ap.add_argument("--max-amount", type=int, default=10,
                     help="amounts in [1, max]; small enough that no sender can underflow, so the final ledger does "
@@ -395,6 +405,7 @@ def main():
     out["start"] = args.start
     out["late_node"] = args.nodes - 1 if args.late_node else None
     out["node_hw_queues"] = args.node_hw_queues or None
+    out["preload_senders"] = bool(args.preload_senders and args.comb)
     out["queue_env"] = {k: v for k, v in os.environ.items() if k.startswith("AT2V_QUEUE")}
     pol_stop.set()
     for pol in pols:
