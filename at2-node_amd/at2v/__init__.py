@@ -261,7 +261,7 @@ def pack_records(pks: Sequence[bytes], sigs: Sequence[bytes], msgs: Sequence[byt
 def launch_streams(count: int = 2, device: Optional[int] = None) -> list:
     """`count` non-blocking HIP streams (hipStreamCreateWithFlags) on `device` (current if None), as
     torch.cuda.ExternalStream objects. Verify launches alternating over them overlap: the context's scratch sets let
-    launch k+1 take the CUs launch k leaves during its end-of-launch drain (at2v_api.hip). Each stream the runtime
+    launch k+1 take the CUs launch k leaves during its end-of-launch drain (at2v_api_launch.h). Each stream the runtime
     creates gets its own hardware queue in turn, which is what lets the two kernels run side by side."""
     import torch
 

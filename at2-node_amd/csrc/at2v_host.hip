@@ -14,6 +14,7 @@
 #include <new>
 
 #include "../../include/at2v.h"
+#include "at2v_device_scope.h"
 #include "at2v_env.h"
 #include "at2v_ledger.h"
 #include "at2v_pack.h"
@@ -36,21 +37,8 @@ struct DevSlot {
 };
 constexpr size_t kSingleCopyMax = 2u << 20;
 
-// Sets the queue's device for a scope and restores the caller's current device on every return path: with launches from
-// the producer's thread (at2v_queue_submit in latency mode) a user thread must not find its HIP device switched
-// (ADVICE r4).
-struct DeviceScope {
-  int prev = -1;
-  hipError_t err;
-  explicit DeviceScope(int device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    err = prev == device ? hipSuccess : hipSetDevice(device);
-  }
-  ~DeviceScope() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
+// sets the queue's device for a scope and restores the caller's current device on every return path
+using at2v::DeviceScope;
 
 struct HipBackend {
   at2v_ctx* ctx = nullptr;

@@ -1,6 +1,6 @@
 """GPU: the multi-device paths that a one-GPU box can still execute (VERDICT r4 "Next round" 1).
 
-* Single process, several devices (`at2v_opts.num_gpus` > 1, at2v_api.hip at2v_verify_batch): the test hook
+* Single process, several devices (`at2v_opts.num_gpus` > 1, at2v_api_hostcall.h at2v_verify_batch): the test hook
   AT2V_TEST_DEVICE_ALIAS=1 maps shard g to device g % ndev, so `num_gpus = 8` runs the real split on device 0: eight
   64-aligned index shards, eight shard streams, eight scratch-set pairs and B tables, eight sender caches, and every
   shard's verdict words copied into its place of the host bitmap. What changes with 8 real devices is only where those

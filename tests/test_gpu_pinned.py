@@ -1,6 +1,6 @@
 """GPU: host-buffer calls on pinned caller memory (ABI 9: at2v_host_alloc / at2v_host_register, include/at2v.h). A
 slice of pk, sig or msg that lies wholly inside one range the context knows is uploaded straight from the caller's memory
-(csrc/at2v_api.hip issue_chunk); everything else takes the staging slot as before. Every test compares record by record
+(csrc/at2v_api_pipe.h issue_chunk); everything else takes the staging slot as before. Every test compares record by record
 with the stored golden verdicts or with the oracle, and checks at2v_info.host_direct_bytes / host_staged_bytes exactly:
 a slice that silently took the other path fails the test even where the verdicts agree.
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """abi_probe.py — the library's host-buffer call (at2v_verify_batch on pageable numpy arrays) under chunk-schedule
-variants, for tuning the HostPipe staging (at2v_api.hip). Each variant sets the test hooks AT2V_TEST_STAGE_FIRST /
+variants, for tuning the HostPipe staging (at2v_api_pipe.h). Each variant sets the test hooks AT2V_TEST_STAGE_FIRST /
 AT2V_TEST_STAGE_MAX / AT2V_TEST_COPY_THREADS (AT2V_TEST_HOOKS=1) before creating its context; variants alternate over
 `--rounds` rounds so box drift hits them alike. Also prints the device-API kernel time of the same batch and a
 single-thread numpy copy rate of the batch (host memory bandwidth).
