@@ -39,6 +39,8 @@ EXPORTED_SYMBOLS = ("at2v_abi_version", "at2v_create", "at2v_destroy", "at2v_ver
                     "at2v_verify_batch_sharded", "at2v_verify_batch_submit", "at2v_verify_batch_wait",
                     "at2v_host_alloc", "at2v_host_free", "at2v_host_register", "at2v_host_unregister",
                     "at2v_sender_preload", "at2v_sender_unpin", "at2v_sender_query", "at2v_queue_sender_preload",
+                    "at2v_transfers_workspace_bytes", "at2v_verify_transfers_device", "at2v_verify_transfers",
+                    "at2v_verify_transfers_submit", "at2v_queue_submit_transfers",
                     "at2v_queue_create", "at2v_queue_destroy", "at2v_queue_submit", "at2v_queue_flush",
                     "at2v_queue_poll", "at2v_queue_get_stats", "at2v_queue_reset_latency",
                     "at2v_pack_send_asset",
@@ -88,7 +90,9 @@ CTX_ADMIT_FIRST = 2    # include/at2v.h AT2V_CTX_ADMIT_FIRST: sender-cache keys 
 CTX_BCOMB_WIDE = 4     # include/at2v.h AT2V_CTX_BCOMB_WIDE: with combs, also a 24-bit-window comb of B (11.8 GB)
 
 
-SMALL_BATCH_DEFAULT = 32768     # include/at2v.h AT2V_SMALL_BATCH_DEFAULT
+WIRE_BYTES, WIRE_ARRAY = 0, 1  # include/at2v.h AT2V_WIRE_*: how a transfer's recipient key is serialised in its message
+
+SMALL_BATCH_DEFAULT = 32768    # include/at2v.h AT2V_SMALL_BATCH_DEFAULT
 SMALL_BATCH_OFF = 0xFFFFFFFF    # include/at2v.h AT2V_SMALL_BATCH_OFF: never use the low-latency kernel
 
 
@@ -178,6 +182,16 @@ def _load(path: str) -> ctypes.CDLL:
     lib.at2v_sender_query.restype = ctypes.c_int
     lib.at2v_verify_batch_device.argtypes = [P, P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, P, P]
     lib.at2v_verify_batch_device.restype = ctypes.c_int
+    lib.at2v_transfers_workspace_bytes.argtypes = [ctypes.c_size_t, ctypes.c_int]
+    lib.at2v_transfers_workspace_bytes.restype = ctypes.c_size_t
+    lib.at2v_verify_transfers_device.argtypes = [P, P, P, P, P, ctypes.c_size_t, ctypes.c_int, P, ctypes.c_size_t, P,
+                                                 P, P]
+    lib.at2v_verify_transfers_device.restype = ctypes.c_int
+    lib.at2v_verify_transfers.argtypes = [P, P, P, P, P, ctypes.c_size_t, ctypes.c_int, P, P]
+    lib.at2v_verify_transfers.restype = ctypes.c_int
+    lib.at2v_verify_transfers_submit.argtypes = [P, P, P, P, P, ctypes.c_size_t, ctypes.c_int, P, P,
+                                                 ctypes.POINTER(ctypes.c_uint64)]
+    lib.at2v_verify_transfers_submit.restype = ctypes.c_int
     lib.at2v_verify_one.argtypes = [P, P, P, ctypes.c_size_t]
     lib.at2v_verify_one.restype = ctypes.c_int
     lib.at2v_verify_one_policy.argtypes = [P, P, P, ctypes.c_size_t, ctypes.c_int]
@@ -291,8 +305,16 @@ class PendingBatch:
     """A submitted host-buffer batch (BatchVerifier.submit_batch): its ticket, verdict words and the arrays the library
     reads until the wait."""
 
-    def __init__(self, ticket: int, n: int, words: np.ndarray, refs: tuple):
+    def __init__(self, ticket: int, n: int, words: np.ndarray, refs: tuple,
+                 recipient_words: Optional[np.ndarray] = None):
         self.ticket, self.n, self.words, self._refs = ticket, n, words, refs
+        self.recipient_words = recipient_words  # submit_transfers(recipient_ok=True): final after wait_batch
+
+    def recipient_ok(self) -> np.ndarray:
+        """bool[n]: which recipients decode (a transfers call submitted with recipient_ok; valid after wait_batch)"""
+        if self.recipient_words is None:
+            raise ValueError("this call was not submitted with recipient_ok")
+        return unpack_verdicts(self.recipient_words, self.n)
 
 
 class BatchVerifier:
@@ -456,6 +478,73 @@ class BatchVerifier:
         """device pointers (e.g. torch tensor data_ptr()), asynchronous on `stream` (a hipStream_t)"""
         _check(self._lib.at2v_verify_batch_device(self._h, d_pk, d_sig, d_msg, msg_bytes, d_off, n, d_verdicts,
                                                   stream or None), "at2v_verify_batch_device")
+
+    # ---- AT2 transfers from their fields (include/at2v.h at2v_verify_transfers*): the node's ledger arrays go in as
+    # they are, the messages bincode(ThinTransaction{recipient, amount}) are built by the library
+    @staticmethod
+    def _transfer_fields(sender, sig, recipient, amount):
+        sender = np.ascontiguousarray(sender, dtype=np.uint8)
+        sig = np.ascontiguousarray(sig, dtype=np.uint8)
+        recipient = np.ascontiguousarray(recipient, dtype=np.uint8)
+        amount = np.ascontiguousarray(amount, dtype=np.uint64).reshape(-1)
+        n = amount.size
+        if sender.size != 32 * n or sig.size != 64 * n or recipient.size != 32 * n:
+            raise ValueError("sender/sig/recipient/amount sizes disagree")
+        return sender, sig, recipient, amount, n
+
+    def _transfer_outputs(self, n: int, words, recipient_ok, recipient_words):
+        words = self._verdict_words(n, words)
+        if recipient_words is not None:
+            recipient_words = self._verdict_words(n, recipient_words)
+        elif recipient_ok:
+            recipient_words = self._verdict_words(n, None)
+        return words, recipient_words
+
+    @staticmethod
+    def transfers_workspace_bytes(n: int, wire: int = WIRE_BYTES) -> int:
+        """at2v_transfers_workspace_bytes: device bytes verify_transfers_device needs for n transfers (0: a bad wire, or
+        an n the device form refuses)"""
+        return int(load_library().at2v_transfers_workspace_bytes(int(n), int(wire)))
+
+    def verify_transfers(self, sender: np.ndarray, sig: np.ndarray, recipient: np.ndarray, amount: np.ndarray,
+                         wire: int = WIRE_BYTES, recipient_ok: bool = False, words: Optional[np.ndarray] = None,
+                         recipient_words: Optional[np.ndarray] = None):
+        """at2v_verify_transfers: sender [n,32], sig [n,64], recipient [n,32] (uint8) and amount [n] (uint64) -> bool[n]
+        verdicts, those of verify_batch over the messages bincode(ThinTransaction{recipient, amount}). recipient_ok
+        (or a recipient_words array): also which recipients decode, returned as a second bool[n]. words /
+        recipient_words: the output words go into these uint32 arrays instead of fresh ones. Arrays of the right dtype
+        that are C-contiguous are passed as they are (host_alloc memory is uploaded from there)."""
+        sender, sig, recipient, amount, n = self._transfer_fields(sender, sig, recipient, amount)
+        words, rw = self._transfer_outputs(n, words, recipient_ok, recipient_words)
+        _check(self._lib.at2v_verify_transfers(self._h, _ptr(sender) or None, _ptr(sig) or None, _ptr(recipient) or None,
+                                               _ptr(amount) or None, n, int(wire), _ptr(words),
+                                               None if rw is None else _ptr(rw)), "at2v_verify_transfers")
+        v = unpack_verdicts(words, n)
+        return v if rw is None else (v, unpack_verdicts(rw, n))
+
+    def submit_transfers(self, sender: np.ndarray, sig: np.ndarray, recipient: np.ndarray, amount: np.ndarray,
+                         wire: int = WIRE_BYTES, recipient_ok: bool = False, words: Optional[np.ndarray] = None,
+                         recipient_words: Optional[np.ndarray] = None) -> "PendingBatch":
+        """at2v_verify_transfers_submit: the pending call (wait_batch returns its verdicts, then
+        PendingBatch.recipient_ok() its recipient bits). Shares the two call slots with submit_batch."""
+        sender, sig, recipient, amount, n = self._transfer_fields(sender, sig, recipient, amount)
+        words, rw = self._transfer_outputs(n, words, recipient_ok, recipient_words)
+        t = ctypes.c_uint64(0)
+        _check(self._lib.at2v_verify_transfers_submit(self._h, _ptr(sender) or None, _ptr(sig) or None,
+                                                      _ptr(recipient) or None, _ptr(amount) or None, n, int(wire),
+                                                      _ptr(words), None if rw is None else _ptr(rw), ctypes.byref(t)),
+               "at2v_verify_transfers_submit")
+        return PendingBatch(t.value, n, words, (sender, sig, recipient, amount), rw)
+
+    def verify_transfers_device(self, d_sender: int, d_sig: int, d_recipient: int, d_amount: int, n: int, wire: int,
+                                d_work: int, work_bytes: int, d_verdicts: int, d_recipient_ok: int = 0,
+                                stream: int = 0) -> None:
+        """at2v_verify_transfers_device: device pointers, asynchronous on `stream`; d_work: work_bytes >=
+        transfers_workspace_bytes(n, wire) of 16-byte-aligned device memory the call may use until the stream gets
+        there; d_recipient_ok: 0 = not asked for"""
+        _check(self._lib.at2v_verify_transfers_device(self._h, d_sender, d_sig, d_recipient, d_amount, n, int(wire),
+                                                      d_work, work_bytes, d_verdicts, d_recipient_ok or None,
+                                                      stream or None), "at2v_verify_transfers_device")
 
     # ---- one rank per GPU: RCCL all-gather of the verdict words (include/at2v.h, SURVEY §8(e))
     def comm_init_rank(self, unique_id: bytes, rank: int, world: int) -> None:

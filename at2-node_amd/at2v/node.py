@@ -105,6 +105,7 @@ def bind(lib) -> None:
         "at2v_queue_create": ([ctypes.POINTER(_QueueOpts), ctypes.POINTER(P)], i32),
         "at2v_queue_destroy": ([P], None),
         "at2v_queue_submit": ([P, P, P, P, P, sz, ctypes.POINTER(u64)], i32),
+        "at2v_queue_submit_transfers": ([P, P, P, P, P, sz, i32, ctypes.POINTER(u64)], i32),
         "at2v_queue_flush": ([P], i32),
         "at2v_queue_poll": ([P, P, P, sz, u32], ctypes.c_long),
         "at2v_queue_poll_reasons": ([P, P, P, sz, u32], ctypes.c_long),
@@ -194,6 +195,22 @@ class IngestQueue:
         m = msg if msg.size else np.zeros(1, np.uint8)
         _chk(self._lib.at2v_queue_submit(self._h, _p(pk), _p(sig), _p(m), _p(off), n, ctypes.byref(first)),
              "at2v_queue_submit")
+        return first.value
+
+    def submit_transfers(self, sender: np.ndarray, sig: np.ndarray, recipient: np.ndarray, amount: np.ndarray,
+                         wire: int = WIRE_BYTES) -> int:
+        """n transfers by their fields (sender [n,32], sig [n,64], recipient [n,32], amount uint64[n]) -> ticket of the
+        first; each message bincode(ThinTransaction{recipient, amount}) is built straight into the queue's slot"""
+        sender = np.ascontiguousarray(sender, np.uint8)
+        sig = np.ascontiguousarray(sig, np.uint8)
+        recipient = np.ascontiguousarray(recipient, np.uint8)
+        amount = np.ascontiguousarray(amount, np.uint64).reshape(-1)
+        n = amount.size
+        if sender.size != 32 * n or sig.size != 64 * n or recipient.size != 32 * n:
+            raise ValueError("sender/sig/recipient/amount sizes disagree")
+        first = ctypes.c_uint64(0)
+        _chk(self._lib.at2v_queue_submit_transfers(self._h, _p(sender), _p(sig), _p(recipient), _p(amount), n,
+                                                   int(wire), ctypes.byref(first)), "at2v_queue_submit_transfers")
         return first.value
 
     def flush(self) -> None:

@@ -7,7 +7,7 @@
 // The code is split by role into pieces that only this file includes, in dependency order (as at2v_kernels.hip does
 // with at2v_kern_*.h). Helpers are in anonymous namespaces and the entry points get their C linkage from the
 // declarations of include/at2v.h, so the library exports the C ABI and nothing else. This file keeps at2v_create,
-// at2v_destroy, at2v_verify_batch_device and at2v_get_info.
+// at2v_destroy, at2v_verify_batch_device, at2v_verify_transfers_device and at2v_get_info.
 //   at2v_device_scope.h  DeviceScope: the caller's current device, restored on every return path (also at2v_host.hip)
 //   at2v_stage_plan.h    HIP-free: chunk schedule, chunk layout, arena bytes, copy pieces of the host-buffer pipeline
 //   at2v_api_ctx.h       DevBuf, Shard, HostCall, at2v_ctx, hip_code / AT2V_TRY, init_shard
@@ -15,7 +15,8 @@
 //   at2v_api_cache.h     SenderCache and its host protocol: claim slots, compaction, thrash guard, control words
 //   at2v_api_launch.h    launch_shard: the one verify launch path (scratch sets, cached launches)
 //   at2v_api_pipe.h      HostPipe: staging slots, SDMA uploads, issue_chunk / flush_chunk, a shard's chunks
-//   at2v_api_hostcall.h  the host-buffer call slots; at2v_verify_batch, at2v_verify_batch_submit / _wait
+//   at2v_api_hostcall.h  the host-buffer call slots; at2v_verify_batch, at2v_verify_batch_submit / _wait, and the same
+//                        for transfers given by their fields: at2v_verify_transfers, at2v_verify_transfers_submit
 //   at2v_api_hostmem.h   pinned host ranges; at2v_host_alloc / _free / _register / _unregister
 //   at2v_api_sender.h    known senders; at2v_sender_preload / _unpin / _query
 //   at2v_api_comm.h      RCCL; at2v_comm_*, at2v_verify_shard_gather_device, at2v_verify_batch_sharded
@@ -133,6 +134,7 @@ void at2v_destroy(at2v_ctx* ctx) {
     for (hipEvent_t ev : s.hcopied)
       if (ev) (void)hipEventDestroy(ev);
     for (DevBuf& b : s.hverdict) b.release();
+    for (DevBuf& b : s.hrok) b.release();
     free_pipe(s);
     free_cache(s.cache);
     for (DevBuf& b : s.scratch) b.release();
@@ -163,6 +165,42 @@ int at2v_verify_batch_device(at2v_ctx* ctx, const uint8_t* d_pk, const uint8_t* 
   hipError_t e = scope.err;
   if (e == hipSuccess)
     e = launch_shard(ctx, s, d_pk, d_sig, d_msg, (uint32_t)msg_bytes, d_msg_off, (uint32_t)n, d_verdicts,
+                     (hipStream_t)hip_stream);
+  return hip_code(e);
+}
+
+// The workspace of the device form: offsets (n + 1) | messages (n x L) | the kernels' 16 bytes of slack, both parts
+// 16-byte aligned.
+size_t at2v_transfers_workspace_bytes(size_t n, int wire) {
+  const size_t len = at2v::transfer_msg_len(wire);
+  if (len == 0 || n >= (1u << 31) || (uint64_t)n * len >= (1ull << 32)) return 0;
+  return (((n + 1) * 4 + 15) & ~(size_t)15) + n * len + 16;
+}
+
+int at2v_verify_transfers_device(at2v_ctx* ctx, const uint8_t* d_sender, const uint8_t* d_sig,
+                                 const uint8_t* d_recipient, const uint64_t* d_amount, size_t n, int wire, void* d_work,
+                                 size_t work_bytes, uint32_t* d_verdicts, uint32_t* d_recipient_ok, void* hip_stream) {
+  if (!ctx) return AT2V_E_INVALID;
+  const size_t len = at2v::transfer_msg_len(wire);
+  if (len == 0) return AT2V_E_INVALID;
+  if (n == 0) return AT2V_OK;
+  const size_t need = at2v_transfers_workspace_bytes(n, wire);  // (0: an n the generated uint32 offsets cannot serve)
+  if (!d_sender || !d_sig || !d_recipient || !d_amount || !d_work || !d_verdicts || need == 0 || work_bytes < need)
+    return AT2V_E_INVALID;
+  if (ctx->shards.empty()) return AT2V_E_NODEVICE;
+  if (!aligned(d_sender, 16) || !aligned(d_sig, 16) || !aligned(d_recipient, 16) || !aligned(d_amount, 8) ||
+      !aligned(d_work, 16) || !aligned(d_verdicts, 4) || (d_recipient_ok && !aligned(d_recipient_ok, 4)))
+    return AT2V_E_ALIGN;
+  Shard& s = ctx->shards[0];
+  const DeviceScope scope(s.device);
+  uint32_t* d_off = static_cast<uint32_t*>(d_work);
+  uint8_t* d_msg = static_cast<uint8_t*>(d_work) + (((n + 1) * 4 + 15) & ~(size_t)15);
+  hipError_t e = scope.err;
+  if (e == hipSuccess)
+    e = at2v::launch_transfer_prep(d_recipient, d_amount, (uint32_t)n, wire, d_msg, d_off, d_recipient_ok,
+                                   (hipStream_t)hip_stream);
+  if (e == hipSuccess)
+    e = launch_shard(ctx, s, d_sender, d_sig, d_msg, (uint32_t)(n * len), d_off, (uint32_t)n, d_verdicts,
                      (hipStream_t)hip_stream);
   return hip_code(e);
 }

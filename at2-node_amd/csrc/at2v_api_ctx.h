@@ -20,6 +20,7 @@
 #include "at2v_hostmem.h"
 #include "at2v_launch.h"
 #include "at2v_stage_plan.h"
+#include "at2v_transfer.h"
 
 namespace {
 
@@ -68,6 +69,7 @@ struct Shard {
   DevBuf hverdict[3];            // host-buffer calls: the shard's device bitmap per call slot (HostCall)
   hipEvent_t hcopied[3] = {nullptr, nullptr, nullptr};  // ... and its verdict copy (the call waits for this, not for
                                                         // the cache builds behind it)
+  DevBuf hrok[3];                // transfers calls that ask for recipient_ok: that bitmap, beside hverdict
   SenderCache* cache = nullptr;
   HostPipe* pipe = nullptr;     // the host-buffer path's streams and staging (created by the first host-buffer call)
 };
@@ -83,6 +85,17 @@ struct HostBatch {  // the caller's arrays of a host-buffer call (at2v_verify_ba
   const uint32_t* msg_off = nullptr;
   size_t n = 0;
   uint32_t* verdicts = nullptr;
+  // a transfers call (at2v_verify_transfers*): pk holds the senders, msg and msg_off are null, and the messages are
+  // built from these fields (at2v_transfer.h) on the device, or on the CPU backend's stack
+  bool transfers = false;
+  const uint8_t* recipient = nullptr;
+  const uint64_t* amount = nullptr;
+  int wire = 0;
+  uint32_t* recipient_ok = nullptr;  // ceil(n / 32) words out, or null
+  // message bytes of records [lo, hi)
+  size_t msg_bytes(size_t lo, size_t hi) const {
+    return transfers ? (hi - lo) * at2v::transfer_msg_len(wire) : (size_t)(msg_off[hi] - msg_off[lo]);
+  }
 };
 struct HostCall {
   bool active = false, done = false;

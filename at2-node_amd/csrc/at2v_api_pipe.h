@@ -35,6 +35,12 @@ struct ChunkLaunch {  // a staged chunk's launch: where its parts are on the dev
   uint32_t* d_words = nullptr;
   bool throughput = false;
   int slot = 0, stream = 0;
+  // a transfers chunk (issue_transfer_chunk): the prep kernel writes off and msg from the recipients at rcp and the
+  // amounts at amt, and the recipient_ok words (or null), right before the verify launch
+  bool transfers = false;
+  size_t rcp = 0, amt = 0;
+  int wire = 0;
+  uint32_t* d_rok = nullptr;
 };
 struct StageSlot {
   uint8_t* host = nullptr;  // pinned
@@ -195,6 +201,9 @@ hipError_t flush_chunk(at2v_ctx* ctx, Shard& s) {
   const auto t0 = clk::now();
   hipError_t e = wait_uploads(p.slot[k.slot]);
   if (ctx->pipe_trace) ctx->tr_wait += std::chrono::duration<double>(clk::now() - t0).count();
+  if (e == hipSuccess && k.transfers)  // the chunk's offsets and messages, from the fields that have just landed
+    e = at2v::launch_transfer_prep(k.d + k.rcp, (const uint64_t*)(k.d + k.amt), (uint32_t)k.c, k.wire, k.d + k.msg,
+                                   (uint32_t*)(k.d + k.off), k.d_rok, p.comp[k.stream]);
   if (e == hipSuccess)
     e = launch_shard(ctx, s, k.d, k.d + k.sig, k.d + k.msg, (uint32_t)k.mb, (const uint32_t*)(k.d + k.off),
                      (uint32_t)k.c, k.d_words, p.comp[k.stream], true, k.throughput);
@@ -308,14 +317,108 @@ hipError_t issue_chunk(at2v_ctx* ctx, Shard& s, at2v::CpuPool* copier, const Hos
   return e;
 }
 
+// The same for records [a, a + c) of a transfers call (b.transfers): the chunk is laid out as transfer_layout gives it, and
+// only the four field arrays are uploaded: senders, signatures, recipients and amounts, each straight from a known pinned
+// range or through the staging slot by the rule above, one upload each. Nothing is rebased on the host: the offsets and
+// the messages are written by the prep kernel that flush_chunk launches before the chunk's verify launch, behind the
+// same upload wait. d_rok: the chunk's recipient_ok words of the shard's second bitmap, or null.
+// The slot's signal counts exactly the uploads that were submitted: when a submit fails, the ones that were never
+// submitted are taken off the count, and the ones in flight still bring it to zero (begin_arena and free_pipe wait for
+// that), so no upload of a failed call is left uncounted while it may still write the arena or read the caller's memory.
+hipError_t issue_transfer_chunk(at2v_ctx* ctx, Shard& s, at2v::CpuPool* copier, const HostBatch& b, size_t a, size_t c,
+                                uint32_t* d_words, uint32_t* d_rok, bool throughput, bool first) {
+  HostPipe& p = *s.pipe;
+  const int k = (int)(p.chunks % kStageSlots);
+  StageSlot& sl = p.slot[k];
+  const size_t len = at2v::transfer_msg_len(b.wire);
+  const at2v::TransferLayout L = at2v::transfer_layout(c, len);
+  // (begin_arena sized it by transfer_arena_bytes, which bounds every plan's layouts: tests/host/transfer_plan_host.cpp)
+  if (p.arena_at + L.total > p.arena().cap) return hipErrorInvalidValue;
+  uint8_t* d = (uint8_t*)p.arena().p + p.arena_at;
+  p.arena_at += (L.total + 255) & ~(size_t)255;
+  using clk = std::chrono::steady_clock;
+  const auto t0 = clk::now();
+  hipError_t e = wait_uploads(sl);  // (done already: the slot's chunk was launched, which waited for them)
+  if (e == hipSuccess && sl.host_cap < L.upload) {
+    if (sl.host) (void)hipHostFree(sl.host);
+    sl.host = nullptr;
+    sl.host_cap = 0;
+    const size_t want = std::max(L.upload + L.upload / 4, chunk_layout(ctx->stage_max, 0).total);
+    e = hipHostMalloc((void**)&sl.host, want, hipHostMallocDefault);
+    if (e == hipSuccess) sl.host_cap = want;
+  }
+  if (e != hipSuccess) return e;
+  const auto t1 = clk::now();
+  struct Part {
+    size_t at;
+    const uint8_t* src;
+    size_t len;
+  };
+  const Part parts[4] = {{0, b.pk + a * 32, c * 32},
+                         {L.sig, b.sig + a * 64, c * 64},
+                         {L.rcp, b.recipient + a * 32, c * 32},
+                         {L.amt, reinterpret_cast<const uint8_t*>(b.amount + a), c * 8}};
+  hsa_signal_store_screlease(sl.uploaded, 4);
+  hipError_t ef = hipSuccess;
+  auto poll = [&]() {
+    if (ef == hipSuccess && p.pending && hsa_signal_load_scacquire(p.slot[p.pend.slot].uploaded) == 0)
+      ef = flush_chunk(ctx, s);
+  };
+  CopyJob job;
+  size_t direct = 0;
+  int submitted = 0;
+  for (const Part& pt : parts) {
+    const at2v::HostRange* r = ctx->hostmem.find(pt.src, pt.len);
+    const uint8_t* src = nullptr;
+    if (r) {
+      src = reinterpret_cast<const uint8_t*>(r->dma + (reinterpret_cast<uintptr_t>(pt.src) - r->base));
+      direct += pt.len;
+    } else {
+      job.add(sl.host + pt.at, pt.src, pt.len);
+      run_copy(copier, job, pt.len, poll);
+      src = sl.host + pt.at;
+    }
+    e = hsa_err(hsa_amd_memory_async_copy(d + pt.at, p.gpu, src, p.cpu, pt.len, 0, nullptr, sl.uploaded));
+    if (e != hipSuccess) break;
+    ++submitted;
+  }
+  if (e == hipSuccess) {
+    ctx->host_direct_bytes += direct;
+    ctx->host_staged_bytes += L.upload - direct;
+    e = ef;
+  }
+  if (e != hipSuccess) {  // the call fails; what was submitted still counts down, what was not never will
+    if (submitted < 4) hsa_signal_subtract_screlease(sl.uploaded, 4 - submitted);
+    return e;
+  }
+  const auto t2 = clk::now();
+  e = flush_chunk(ctx, s);
+  p.pend = ChunkLaunch{d, L.sig, L.off, L.msg, c * len, c, d_words, throughput, k, (int)(p.chunks % 2),
+                       true, L.rcp, L.amt, b.wire, d_rok};
+  p.pending = true;
+  if (e == hipSuccess && first) e = flush_chunk(ctx, s);
+  ++p.chunks;
+  ++ctx->host_chunks;
+  if (ctx->pipe_trace) {
+    const auto t3 = clk::now();
+    ctx->tr_wait += std::chrono::duration<double>(t1 - t0).count();
+    ctx->tr_copy += std::chrono::duration<double>(t2 - t1).count();
+    ctx->tr_enq += std::chrono::duration<double>(t3 - t2).count();
+  }
+  return e;
+}
+
 // The pipe's arena for a shard's part of a call (m records, mb message bytes), before its first chunk: every launch of
-// the previous host-buffer call has completed (the call waited for its verdict copy, which followed them).
-hipError_t begin_arena(at2v_ctx* ctx, Shard& s, size_t m, size_t mb) {
+// the previous host-buffer call has completed (the call waited for its verdict copy, which followed them). transfers:
+// the part's chunks are transfer_layouts (mb = m x the message length).
+hipError_t begin_arena(at2v_ctx* ctx, Shard& s, size_t m, size_t mb, bool transfers = false) {
   HostPipe& p = *s.pipe;
   for (StageSlot& sl : p.slot) (void)wait_uploads(sl);  // (after a failed call, uploads may still write the arena)
   p.pending = false;
   p.arena_at = 0;
-  return p.arena().ensure(at2v::arena_bytes(m, mb, std::min(ctx->stage_first, std::max<size_t>(m, 1))));
+  const size_t first = std::min(ctx->stage_first, std::max<size_t>(m, 1));
+  return p.arena().ensure(transfers ? at2v::transfer_arena_bytes(m, mb / std::max<size_t>(m, 1), first)
+                                    : at2v::arena_bytes(m, mb, first));
 }
 
 at2v::CpuPool* copy_pool(at2v_ctx* ctx) {
@@ -328,8 +431,11 @@ at2v::CpuPool* copy_pool(at2v_ctx* ctx) {
 // verdict words go to d_words. A call over several shards issues their chunks in turn, so every device's pipeline fills
 // early (host_call_issue).
 hipError_t issue_next_chunk(at2v_ctx* ctx, Shard& s, at2v::CpuPool* copier, const HostBatch& b, ChunkPlan& cp,
-                            size_t lo, uint32_t* d_words) {
+                            size_t lo, uint32_t* d_words, uint32_t* d_rok = nullptr) {
   const size_t at = cp.pos, c = cp.take();
+  if (b.transfers)
+    return issue_transfer_chunk(ctx, s, copier, b, lo + at, c, d_words + at / 32, d_rok ? d_rok + at / 32 : nullptr,
+                                cp.m > ctx->pair_max, at == 0);
   return issue_chunk(ctx, s, copier, b, lo + at, c, d_words + at / 32, cp.m > ctx->pair_max, at == 0);
 }
 

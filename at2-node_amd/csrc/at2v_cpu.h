@@ -32,6 +32,12 @@ void pool_run(CpuPool* p, size_t chunks, void (*fn)(void*, size_t), void* arg);
 void cpu_verify_batch(CpuPool* p, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, const uint32_t* msg_off,
                       size_t n, int policy, uint32_t* verdicts);
 
+// The same over the fields of n transfers (at2v_verify_transfers): record i's message is built on the stack from
+// recipient i and amount i (at2v_transfer.h; wire: AT2V_WIRE_BYTES or AT2V_WIRE_ARRAY, checked by the caller) and goes
+// through the same verify routine. Whether the recipient decodes does not enter the verdict (cpu_decode_points tells).
+void cpu_verify_transfers(CpuPool* p, const uint8_t* sender, const uint8_t* sig, const uint8_t* recipient,
+                          const uint64_t* amount, size_t n, int wire, int policy, uint32_t* verdicts);
+
 // bit i of valid_words = 1 iff pts[i] decodes under dalek rules (the kernels' gu_frombytes), synchronous
 void cpu_decode_points(CpuPool* p, const uint8_t* pts, size_t n, uint32_t* valid_words);
 

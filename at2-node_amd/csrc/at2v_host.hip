@@ -367,6 +367,14 @@ int at2v_queue_submit(at2v_queue* q, const uint8_t* pk, const uint8_t* sig, cons
   return q->q->submit(pk, sig, msg, msg_off, n, first_ticket) == 0 ? AT2V_OK : AT2V_E_INVALID;
 }
 
+int at2v_queue_submit_transfers(at2v_queue* q, const uint8_t* sender, const uint8_t* sig, const uint8_t* recipient,
+                                const uint64_t* amount, size_t n, int wire, uint64_t* first_ticket) {
+  if (!q || !q->q || at2v::transfer_msg_len(wire) == 0) return AT2V_E_INVALID;
+  if (n == 0) return AT2V_OK;
+  if (!sender || !sig || !recipient || !amount) return AT2V_E_INVALID;
+  return q->q->submit_transfers(sender, sig, recipient, amount, n, wire, first_ticket) == 0 ? AT2V_OK : AT2V_E_INVALID;
+}
+
 int at2v_queue_flush(at2v_queue* q) {
   if (!q || !q->q) return AT2V_E_INVALID;
   q->q->flush();

@@ -29,6 +29,7 @@
 #include "at2v_kern_comb.h"
 #include "at2v_kern_sign.h"
 #include "at2v_kern_btab.h"
+#include "at2v_kern_transfer.h"
 
 namespace at2v {
 

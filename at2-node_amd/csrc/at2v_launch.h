@@ -35,6 +35,12 @@ hipError_t launch_sign(const uint8_t* seeds, const uint8_t* msg, uint32_t msg_to
                        uint8_t* pk, uint8_t* sig, hipStream_t stream);
 hipError_t launch_decode(const uint8_t* pts, uint32_t n, uint32_t* out, hipStream_t stream);
 
+// ---- transfers (at2v_kern_transfer.h): the messages and offsets of n transfers from their fields, for the verify launch
+// that follows on `stream`. msg: 16-byte aligned, n * L bytes (L = 48 or 40 by wire, n * L < 2^32); off: n + 1 words;
+// recipient_ok: ceil(n / 32) words (bit i: recipient i decodes), or nullptr
+hipError_t launch_transfer_prep(const uint8_t* recipient, const uint64_t* amount, uint32_t n, int wire, uint8_t* msg,
+                                uint32_t* off, uint32_t* recipient_ok, hipStream_t stream);
+
 // ---- combs of B
 size_t bcomb_bytes(int bits);  // a comb of B with bits-bit windows (16, 20 or 24)
 int bcomb_lat_bits();

@@ -26,6 +26,8 @@
 #include <utility>
 #include <vector>
 
+#include "at2v_transfer.h"
+
 namespace at2v {
 
 inline uint64_t now_us() {
@@ -113,69 +115,58 @@ class BatchQueue {
   // Append n records (ABI layout; msg_off has n+1 entries, message i = msg[off[i]..off[i+1])).
   int submit(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, const uint32_t* off, size_t n,
              uint64_t* first_ticket) {
-    // one call's records get consecutive tickets: producers are serialised for the whole call (a call
-    // may block for a free slot, and nobody else may take tickets meanwhile)
-    std::lock_guard<std::mutex> producer(submit_m_);
-    std::unique_lock<std::mutex> lk(m_);
-    if (!running_) return -1;
-    for (size_t i = 0; i < n; ++i)  // validate the whole call before taking any record
-      if (off[i + 1] < off[i] || off[i + 1] - off[i] > slots_[0].cap_msg) return -1;
-    if (first_ticket) *first_ticket = next_ticket_;
-    const uint64_t t = now_us();  // one submit time for the whole call
-    size_t i = 0;
-    while (i < n) {
-      if (fill_ && (fill_->n == fill_->cap_records || fill_->msg_used + (off[i + 1] - off[i]) > fill_->cap_msg))
-        seal_locked();
-      if (!fill_) {
-        cv_free_.wait(lk, [&] { return fill_ || !free_.empty() || !running_; });
-        if (!running_) return -1;
+    struct Src {  // messages from the caller's concatenated array
+      const uint8_t* msg;
+      const uint32_t* off;
+      bool valid(size_t n, size_t cap_msg) const {
+        for (size_t i = 0; i < n; ++i)
+          if (off[i + 1] < off[i] || off[i + 1] - off[i] > cap_msg) return false;
+        return true;
       }
-      if (!fill_) {
-        fill_ = free_.front();
-        free_.pop_front();
-        fill_->n = 0;
-        fill_->msg_used = 0;
-        fill_->first_ticket = next_ticket_;
-        fill_->t_runs.clear();
-        fill_->off[0] = 0;
-      }
-      QueueSlot& s = *fill_;
-      if (s.n == 0) {
-        s.t_first = t;
-        cv_launch_.notify_all();  // arm the deadline
-      }
-      // bulk-copy the longest run of records that fits the slot (records and message bytes)
-      size_t m = std::min(n - i, s.cap_records - s.n);
-      const size_t room = s.cap_msg - s.msg_used;
-      if (off[i + m] - off[i] > room) {  // offsets are non-decreasing: binary search the message-byte limit
-        size_t lo = 1, hi = m;             // off[i+1]-off[i] <= room holds (checked above)
-        while (lo < hi) {
+      size_t len(size_t i) const { return off[i + 1] - off[i]; }
+      size_t run(size_t i, size_t m, size_t room) const {
+        if (off[i + m] - off[i] <= room) return m;
+        size_t lo = 1, hi = m;  // offsets are non-decreasing: binary search the message-byte limit
+        while (lo < hi) {       // off[i+1]-off[i] <= room holds (the slot was sealed otherwise)
           const size_t mid = (lo + hi + 1) / 2;
           if (off[i + mid] - off[i] <= room) lo = mid; else hi = mid - 1;
         }
-        m = lo;
+        return lo;
       }
-      const uint32_t mb = off[i + m] - off[i];
-      std::memcpy(s.pk + 32 * s.n, pk + 32 * i, 32 * m);
-      std::memcpy(s.sig + 64 * s.n, sig + 64 * i, 64 * m);
-      if (mb) std::memcpy(s.msg + s.msg_used, msg + off[i], mb);
-      const uint32_t base = (uint32_t)s.msg_used - off[i];
-      for (size_t k = 1; k <= m; ++k) s.off[s.n + k] = off[i + k] + base;
-      s.msg_used += mb;
-      s.n += m;
-      s.t_runs.emplace_back((uint32_t)m, t);
-      next_ticket_ += m;
-      stats_.submitted += m;
-      i += m;
-      if (s.n == s.cap_records) seal_locked();
-    }
-    // latency mode with the device idle: this thread seals and launches the batch itself instead of waking the
-    // launcher thread (one thread hand-off less per lone batch); if a launch is under way the launcher takes it
-    if (o_.eager && o_.launch_here && fill_ && fill_->n && ready_.empty() && inflight_.empty() && !launching_) {
-      seal_locked();
-      launch_here_locked(lk);
-    }
-    return 0;
+      uint32_t write(QueueSlot& s, size_t i, size_t m) const {  // messages and offsets of records [i, i + m)
+        const uint32_t mb = off[i + m] - off[i];
+        if (mb) std::memcpy(s.msg + s.msg_used, msg + off[i], mb);
+        const uint32_t base = (uint32_t)s.msg_used - off[i];
+        for (size_t k = 1; k <= m; ++k) s.off[s.n + k] = off[i + k] + base;
+        return mb;
+      }
+    };
+    return submit_from(pk, sig, n, first_ticket, Src{msg, off});
+  }
+
+  // Append n transfers from their fields (at2v_queue_submit_transfers): sender and signature as pk and sig above, and
+  // each record's message is built from recipient i and amount i straight into the filling slot's message region
+  // (at2v_transfer.h; len = transfer_msg_len(wire), checked by the caller to be 48 or 40). A message that exceeds the
+  // slot's message capacity is refused like an oversize message of submit().
+  int submit_transfers(const uint8_t* pk, const uint8_t* sig, const uint8_t* recipient, const uint64_t* amount,
+                       size_t n, int wire, uint64_t* first_ticket) {
+    struct Src {
+      const uint8_t* recipient;
+      const uint64_t* amount;
+      int wire;
+      size_t L;
+      bool valid(size_t, size_t cap_msg) const { return L != 0 && L <= cap_msg; }
+      size_t len(size_t) const { return L; }
+      size_t run(size_t, size_t m, size_t room) const { return std::min(m, room / L); }
+      uint32_t write(QueueSlot& s, size_t i, size_t m) const {
+        for (size_t k = 0; k < m; ++k) {
+          transfer_msg_bytes(s.msg + s.msg_used + k * L, recipient + 32 * (i + k), amount[i + k], wire);
+          s.off[s.n + k + 1] = (uint32_t)(s.msg_used + (k + 1) * L);
+        }
+        return (uint32_t)(m * L);
+      }
+    };
+    return submit_from(pk, sig, n, first_ticket, Src{recipient, amount, wire, transfer_msg_len(wire)});
   }
 
   // Seal the filling batch now (non-blocking).
@@ -256,6 +247,60 @@ class BatchQueue {
   }
 
  private:
+  // The one submit path: n records whose messages come from src (the caller's message array, or transfer fields).
+  template <class Src>
+  int submit_from(const uint8_t* pk, const uint8_t* sig, size_t n, uint64_t* first_ticket, const Src& src) {
+    // one call's records get consecutive tickets: producers are serialised for the whole call (a call
+    // may block for a free slot, and nobody else may take tickets meanwhile)
+    std::lock_guard<std::mutex> producer(submit_m_);
+    std::unique_lock<std::mutex> lk(m_);
+    if (!running_) return -1;
+    if (!src.valid(n, slots_[0].cap_msg)) return -1;  // validate the whole call before taking any record
+    if (first_ticket) *first_ticket = next_ticket_;
+    const uint64_t t = now_us();  // one submit time for the whole call
+    size_t i = 0;
+    while (i < n) {
+      if (fill_ && (fill_->n == fill_->cap_records || fill_->msg_used + src.len(i) > fill_->cap_msg))
+        seal_locked();
+      if (!fill_) {
+        cv_free_.wait(lk, [&] { return fill_ || !free_.empty() || !running_; });
+        if (!running_) return -1;
+      }
+      if (!fill_) {
+        fill_ = free_.front();
+        free_.pop_front();
+        fill_->n = 0;
+        fill_->msg_used = 0;
+        fill_->first_ticket = next_ticket_;
+        fill_->t_runs.clear();
+        fill_->off[0] = 0;
+      }
+      QueueSlot& s = *fill_;
+      if (s.n == 0) {
+        s.t_first = t;
+        cv_launch_.notify_all();  // arm the deadline
+      }
+      // bulk-copy the longest run of records that fits the slot (records and message bytes)
+      const size_t m = src.run(i, std::min(n - i, s.cap_records - s.n), s.cap_msg - s.msg_used);
+      std::memcpy(s.pk + 32 * s.n, pk + 32 * i, 32 * m);
+      std::memcpy(s.sig + 64 * s.n, sig + 64 * i, 64 * m);
+      s.msg_used += src.write(s, i, m);
+      s.n += m;
+      s.t_runs.emplace_back((uint32_t)m, t);
+      next_ticket_ += m;
+      stats_.submitted += m;
+      i += m;
+      if (s.n == s.cap_records) seal_locked();
+    }
+    // latency mode with the device idle: this thread seals and launches the batch itself instead of waking the
+    // launcher thread (one thread hand-off less per lone batch); if a launch is under way the launcher takes it
+    if (o_.eager && o_.launch_here && fill_ && fill_->n && ready_.empty() && inflight_.empty() && !launching_) {
+      seal_locked();
+      launch_here_locked(lk);
+    }
+    return 0;
+  }
+
   struct Done {
     uint64_t first;
     size_t n, used;

@@ -41,6 +41,31 @@ inline size_t arena_bytes(size_t m, size_t mb, size_t first) {
   return m * 100 + mb + chunks * (16 + 4 + 16 + 256) + 256;
 }
 
+// A chunk of c transfers (at2v_verify_transfers*; message length L = 48 or 40): pk | sig | recipient | amount, which are
+// uploaded (c * 136 bytes in a row, the staging slot's layout too), then the offsets (c + 1) and the messages (c * L, + 16
+// bytes of slack) that the prep kernel writes on the device. Every part 16-byte aligned.
+struct TransferLayout {
+  size_t sig, rcp, amt, upload, off, msg, total;
+};
+inline TransferLayout transfer_layout(size_t c, size_t L) {
+  TransferLayout l;
+  l.sig = c * 32;
+  l.rcp = c * 96;
+  l.amt = c * 128;
+  l.upload = c * 136;
+  l.off = (l.upload + 15) & ~(size_t)15;
+  l.msg = (l.off + (c + 1) * 4 + 15) & ~(size_t)15;
+  l.total = l.msg + c * L + 16;
+  return l;
+}
+
+// device bytes a shard's part of a transfers call takes in the pipe's arena: every chunk's transfer_layout, 256-aligned
+// (per chunk: up to 15 + 15 bytes of alignment, the extra offset, the slack, and up to 255 bytes to the next region)
+inline size_t transfer_arena_bytes(size_t m, size_t L, size_t first) {
+  const size_t chunks = m / (first ? first : 1) + 2;
+  return m * (140 + L) + chunks * (15 + 15 + 4 + 16 + 256) + 256;
+}
+
 // The chunk schedule of one shard's part of a host batch: a part the low-latency kernel takes whole (<= pair_max, the
 // context's small_batch_max, records) is one chunk; a larger one starts with stage_first (kStageFirstRecords: the
 // pipeline's fill, nothing runs on the device until it is up), then doubles up to stage_max (kStageMaxRecords), and a

@@ -293,6 +293,20 @@ extern "C" {
     pub fn at2v_sender_preload(ctx: *mut At2vCtx, pk: *const u8, n: usize, flags: u32, status: *mut u8) -> c_int;
     pub fn at2v_sender_unpin(ctx: *mut At2vCtx, pk: *const u8, n: usize) -> c_int;
     pub fn at2v_sender_query(ctx: *mut At2vCtx, pk: *const u8, n: usize, status: *mut u8) -> c_int;
+    // AT2 transfers from their fields, also added within ABI version 9
+    pub fn at2v_transfers_workspace_bytes(n: usize, wire: c_int) -> usize;
+    pub fn at2v_verify_transfers_device(ctx: *mut At2vCtx, d_sender: *const u8, d_sig: *const u8,
+                                        d_recipient: *const u8, d_amount: *const u64, n: usize, wire: c_int,
+                                        d_work: *mut c_void, work_bytes: usize, d_verdicts: *mut u32,
+                                        d_recipient_ok: *mut u32, hip_stream: *mut c_void) -> c_int;
+    pub fn at2v_verify_transfers(ctx: *mut At2vCtx, sender: *const u8, sig: *const u8, recipient: *const u8,
+                                 amount: *const u64, n: usize, wire: c_int, verdicts: *mut u32,
+                                 recipient_ok: *mut u32) -> c_int;
+    pub fn at2v_verify_transfers_submit(ctx: *mut At2vCtx, sender: *const u8, sig: *const u8, recipient: *const u8,
+                                        amount: *const u64, n: usize, wire: c_int, verdicts: *mut u32,
+                                        recipient_ok: *mut u32, ticket: *mut u64) -> c_int;
+    pub fn at2v_queue_submit_transfers(q: *mut At2vQueue, sender: *const u8, sig: *const u8, recipient: *const u8,
+                                       amount: *const u64, n: usize, wire: c_int, first_ticket: *mut u64) -> c_int;
     pub fn at2v_verify_batch_device(ctx: *mut At2vCtx, d_pk: *const u8, d_sig: *const u8, d_msg: *const u8,
                                     msg_bytes: usize, d_msg_off: *const u32, n: usize, d_verdicts: *mut u32,
                                     hip_stream: *mut c_void) -> c_int;
@@ -403,6 +417,20 @@ fn check_records(pk: &[u8], sig: &[u8], msg: &[u8], msg_off: &[u32]) -> Result<u
     Ok(n)
 }
 
+/// The field arrays of n transfers (at2v_verify_transfers, at2v_queue_submit_transfers): the C side reads n x 32, n x 64,
+/// n x 32 bytes and n amounts and takes no lengths, so a safe wrapper checks them all against `amount.len()`, and the
+/// wire, before it hands the pointers over.
+fn check_transfers(sender: &[u8], sig: &[u8], recipient: &[u8], amount: &[u64], wire: c_int) -> Result<usize, Error> {
+    let n = amount.len();
+    if sender.len() != 32 * n || sig.len() != 64 * n || recipient.len() != 32 * n {
+        return Err(Error(AT2V_E_INVALID));
+    }
+    if wire != AT2V_WIRE_BYTES && wire != AT2V_WIRE_ARRAY {
+        return Err(Error(AT2V_E_INVALID));
+    }
+    Ok(n)
+}
+
 fn check_abi() -> Result<(), Error> {
     if unsafe { at2v_abi_version() } != AT2V_ABI_VERSION {
         return Err(Error(AT2V_E_INVALID));
@@ -467,6 +495,23 @@ impl BatchVerifier {
         };
         check(rc)?;
         Ok((0..n).map(|i| (words[i / 32] >> (i % 32)) & 1 == 1).collect())
+    }
+
+    /// AT2 transfers by their fields (at2v_verify_transfers): `sender` n x 32, `sig` n x 64, `recipient` n x 32 bytes,
+    /// `amount` n values; `wire` = AT2V_WIRE_BYTES or AT2V_WIRE_ARRAY. The library builds each signed message
+    /// bincode(ThinTransaction{recipient, amount}) itself. Returns one verdict per record (those of `verify` over the
+    /// same messages) and, per record, whether the recipient key decodes (what deserialising it checks at rpc.rs:265).
+    pub fn verify_transfers(&mut self, sender: &[u8], sig: &[u8], recipient: &[u8], amount: &[u64], wire: c_int)
+                            -> Result<(Vec<bool>, Vec<bool>), Error> {
+        let n = check_transfers(sender, sig, recipient, amount, wire)?;
+        let mut words = vec![0u32; (n + 31) / 32];
+        let mut rok = vec![0u32; (n + 31) / 32];
+        check(unsafe {
+            at2v_verify_transfers(self.0, sender.as_ptr(), sig.as_ptr(), recipient.as_ptr(), amount.as_ptr(), n, wire,
+                                  words.as_mut_ptr(), rok.as_mut_ptr())
+        })?;
+        let bits = |w: &Vec<u32>| (0..n).map(|i| (w[i / 32] >> (i % 32)) & 1 == 1).collect::<Vec<bool>>();
+        Ok((bits(&words), bits(&rok)))
     }
 
     /// Device-resident records (the layout of `verify`, in HBM of the context's first device), asynchronous on
@@ -615,6 +660,18 @@ impl Queue {
         Ok(first)
     }
 
+    /// Transfers by their fields (the arrays of `BatchVerifier::verify_transfers`); returns the ticket of the first.
+    pub fn submit_transfers(&self, sender: &[u8], sig: &[u8], recipient: &[u8], amount: &[u64], wire: c_int)
+                            -> Result<u64, Error> {
+        let n = check_transfers(sender, sig, recipient, amount, wire)?;
+        let mut first = 0u64;
+        check(unsafe {
+            at2v_queue_submit_transfers(self.0, sender.as_ptr(), sig.as_ptr(), recipient.as_ptr(), amount.as_ptr(), n,
+                                        wire, &mut first)
+        })?;
+        Ok(first)
+    }
+
     pub fn flush(&self) -> Result<(), Error> {
         check(unsafe { at2v_queue_flush(self.0) }).map(|_| ())
     }
@@ -690,5 +747,18 @@ mod tests {
         assert!(check_records(&pk, &sig, &msg, &[3, 2]).is_err()); // decreasing
         assert!(check_records(&pk, &sig[..32], &msg, &[0, 4]).is_err()); // short signature
         assert!(check_records(&[], &[], &[], &[]).is_ok()); // an empty batch
+    }
+
+    /// The transfers calls take four arrays and no lengths: every one must match `amount.len()`, and the wire is checked.
+    #[test]
+    fn safe_layer_rejects_mismatched_transfer_arrays() {
+        let (sender, sig, recipient, amount) = ([0u8; 64], [0u8; 128], [0u8; 64], [1u64, 2]);
+        assert_eq!(check_transfers(&sender, &sig, &recipient, &amount, AT2V_WIRE_BYTES).ok(), Some(2));
+        assert!(check_transfers(&sender, &sig, &recipient, &amount, AT2V_WIRE_ARRAY).is_ok());
+        assert!(check_transfers(&sender, &sig, &recipient[..32], &amount, AT2V_WIRE_BYTES).is_err()); // short recipients
+        assert!(check_transfers(&sender[..32], &sig, &recipient, &amount, AT2V_WIRE_BYTES).is_err());
+        assert!(check_transfers(&sender, &sig, &recipient, &amount[..1], AT2V_WIRE_BYTES).is_err());
+        assert!(check_transfers(&sender, &sig, &recipient, &amount, 2).is_err()); // not a wire
+        assert!(check_transfers(&[], &[], &[], &[], AT2V_WIRE_BYTES).is_ok()); // an empty batch
     }
 }

@@ -29,7 +29,8 @@ extern "C" {
  * version 9 added the pinned host memory calls (at2v_host_alloc / _free / _register / _unregister) and appended
  * at2v_info.host_direct_bytes / host_staged_bytes; the known-senders calls (at2v_sender_preload / _unpin / _query,
  * at2v_queue_sender_preload) were added within version 9: they touch no struct, so the number did not move, and a
- * binding that needs them checks that the library exports them;
+ * binding that needs them checks that the library exports them; so were the transfers calls (at2v_verify_transfers /
+ * _submit / _device, at2v_transfers_workspace_bytes, at2v_queue_submit_transfers);
  * version 8 added the reject reasons (at2v_reject_reasons / _device, at2v_verify_one_reason, at2v_reason_name,
  * at2v_queue_poll_reasons with the AT2V_QUEUE_REASONS queue flag; no struct changed);
  * version 7 appended at2v_info.experiments / host_chunks (and the AT2V_EXPERIMENT_* bits) and added
@@ -240,6 +241,57 @@ int at2v_verify_batch_device(at2v_ctx* ctx, const uint8_t* d_pk, const uint8_t* 
                              size_t msg_bytes, const uint32_t* d_msg_off, size_t n, uint32_t* d_verdicts,
                              void* hip_stream);
 
+/* ---- AT2 transfers from their fields (added within ABI version 9: no struct changed) ----
+ * A node holds its traffic as the fields of SendAssetRequest (sender, recipient, amount, signature; at2.proto:10-16), the
+ * struct-of-arrays at2v_ledger_deliver consumes, not as messages. The signed message is always
+ * M = bincode(ThinTransaction{recipient, amount}) (src/lib.rs:14-22): with wire = AT2V_WIRE_BYTES the L = 48 bytes
+ * u64le(32) || recipient || u64le(amount), with wire = AT2V_WIRE_ARRAY the L = 40 bytes recipient || u64le(amount) (the
+ * enum is declared with the packer below; any other wire is AT2V_E_INVALID). These calls take the fields as they are and
+ * build M themselves, beside the records: no message array, no offsets, 136 bytes of upload per record.
+ *   sender     n x 32 bytes, laid out as pk elsewhere          sig     n x 64 bytes, as elsewhere
+ *   recipient  n x 32 bytes                                    amount  n native-endian uint64_t
+ * Verdicts: the verdict of record i is exactly that of at2v_verify_batch over (sender_i, sig_i, M_i) under the context's
+ * policy, on every route a context takes (sender tables and combs, the partitioned launch, both small-batch kernels,
+ * several devices, the CPU backend). It is a pure function of those bytes: whether the recipient decodes does not enter it.
+ * recipient_ok (may be NULL): when given it receives ceil(n/32) words; bit i is 1 iff recipient_i decodes under dalek's
+ * rules (CompressedEdwardsY::decompress; the answer of at2v_decode_points, what deserialising the key checks at
+ * rpc.rs:265). Pad bits are 0 and nothing is written past the words.
+ *
+ * at2v_verify_transfers_device: device buffers of ctx's first device, asynchronous on `hip_stream` like
+ * at2v_verify_batch_device (AT2V_E_NODEVICE on a CPU context; n = 0 is AT2V_OK). A prep kernel writes the n + 1 offsets
+ * and the messages into d_work, then the verify launch follows on the same stream. d_work is caller-owned device memory,
+ * 16-byte aligned, of at least at2v_transfers_workspace_bytes(n, wire) bytes (work_bytes says how many it has; less is
+ * AT2V_E_INVALID); it must stay untouched until the stream reaches this point. The library allocates nothing on this path
+ * and writes nothing past work_bytes. d_sender, d_sig and d_recipient 16-byte aligned, d_amount 8-byte, the two bitmaps
+ * 4-byte (AT2V_E_ALIGN). The generated offsets are uint32: n < 2^31 and n x L < 2^32, otherwise AT2V_E_INVALID (and
+ * at2v_transfers_workspace_bytes returns 0, as for a bad wire). The prep kernel takes none of the context's scratch sets
+ * and adds no ordering between verify launches.
+ *
+ * at2v_verify_transfers / at2v_verify_transfers_submit: host buffers, n < 2^31 (chunks carry their own offsets). They go
+ * through the call slots of at2v_verify_batch / at2v_verify_batch_submit: the synchronous form completes the calls in
+ * flight first, a submit returns a ticket that at2v_verify_batch_wait waits for, at most two calls are in flight, and a
+ * transfers call and a records call may be in flight together. Only the four field arrays are uploaded, each per chunk
+ * straight from a range of at2v_host_alloc / at2v_host_register or through a staging slot by the rule above; all four
+ * count in at2v_info.host_direct_bytes / host_staged_bytes, and nothing is rebased on the host. A CPU context verifies on
+ * its thread pool with no HIP call. With AT2V_CTX_CPU_FALLBACK a failed device call is verified again on the CPU from the
+ * caller's fields, recipient_ok included. These calls fail closed: whenever a call that was started does not end in
+ * AT2V_OK, every verdict word and every recipient_ok word of the call is 0, also when a later submit completes it and its
+ * result code is lost. (An argument error is returned before anything is started and leaves the outputs untouched.)
+ *
+ * at2v_queue_submit_transfers: at2v_queue_submit for n transfers. The messages are built on the host straight into the
+ * filling slot's message region; the records get consecutive tickets and everything downstream (poll, reasons, the CPU
+ * queue, the fallback) is unchanged. A queue whose slots cannot hold one message of L bytes refuses the call as
+ * at2v_queue_submit refuses an oversize message (AT2V_E_INVALID). */
+size_t at2v_transfers_workspace_bytes(size_t n, int wire);
+int at2v_verify_transfers_device(at2v_ctx* ctx, const uint8_t* d_sender, const uint8_t* d_sig,
+                                 const uint8_t* d_recipient, const uint64_t* d_amount, size_t n, int wire, void* d_work,
+                                 size_t work_bytes, uint32_t* d_verdicts, uint32_t* d_recipient_ok, void* hip_stream);
+int at2v_verify_transfers(at2v_ctx* ctx, const uint8_t* sender, const uint8_t* sig, const uint8_t* recipient,
+                          const uint64_t* amount, size_t n, int wire, uint32_t* verdicts, uint32_t* recipient_ok);
+int at2v_verify_transfers_submit(at2v_ctx* ctx, const uint8_t* sender, const uint8_t* sig, const uint8_t* recipient,
+                                 const uint64_t* amount, size_t n, int wire, uint32_t* verdicts,
+                                 uint32_t* recipient_ok, uint64_t* ticket);
+
 /* One signature on the CPU, synchronous: 1 = valid, 0 = invalid, < 0 = error. The drop-in for the
  * per-signature `Signature::verify(&message, &public_key)` that drop exposes and sieve/murmur call per payload
  * ("CPU, 1/0"), for callers that verify one payload at a time, e.g. the A/sig decode at
@@ -434,6 +486,10 @@ void at2v_queue_destroy(at2v_queue* q); /* seals and completes everything submit
  * records get consecutive tickets). Blocks only while every slot is busy (backpressure). */
 int at2v_queue_submit(at2v_queue* q, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg,
                       const uint32_t* msg_off, size_t n, uint64_t* first_ticket);
+/* The same for n transfers given by their fields ("AT2 transfers from their fields" above): sender / sig / recipient /
+ * amount as at2v_verify_transfers takes them, wire = AT2V_WIRE_BYTES or AT2V_WIRE_ARRAY. */
+int at2v_queue_submit_transfers(at2v_queue* q, const uint8_t* sender, const uint8_t* sig, const uint8_t* recipient,
+                                const uint64_t* amount, size_t n, int wire, uint64_t* first_ticket);
 int at2v_queue_flush(at2v_queue* q);
 /* Up to max completed (ticket, verdict) pairs in ticket order, waiting up to timeout_us for the first.
  * verdict: 1 valid, 0 invalid, 0xff the batch failed on the device. Returns the count (>= 0) or < 0. */
