@@ -125,16 +125,14 @@ void host_call_finish(at2v_ctx* ctx, int k) {
     ++ctx->cpu_fallbacks;
     rc = AT2V_OK;
   }
-  if (rc != AT2V_OK && hc.b.transfers) {
-    // a transfers call fails closed: once nothing of it can land any more, every word of both outputs is 0 (also when a
+  if (rc != AT2V_OK) {
+    // a host-buffer call fails closed: once nothing of it can land any more, every word of its outputs is 0 (also when a
     // later submit completes the call and its result code is lost)
     drain_shard_streams(ctx);
     const size_t words = (hc.b.n + 31) / 32;
     std::memset(hc.b.verdicts, 0, words * 4);
     if (hc.b.recipient_ok) std::memset(hc.b.recipient_ok, 0, words * 4);
   }
-  // TODO: a records call that fails without the CPU fallback does not zero the caller's verdict words (VERDICT "What's
-  // weak" 8)
   hc.rc = rc;
   hc.done = true;
 }

@@ -35,8 +35,8 @@ struct ChunkLaunch {  // a staged chunk's launch: where its parts are on the dev
   uint32_t* d_words = nullptr;
   bool throughput = false;
   int slot = 0, stream = 0;
-  // a transfers chunk (issue_transfer_chunk): the prep kernel writes off and msg from the recipients at rcp and the
-  // amounts at amt, and the recipient_ok words (or null), right before the verify launch
+  // a transfers chunk: the prep kernel writes off and msg from the recipients at rcp and the amounts at amt, and the
+  // recipient_ok words (or null), right before the verify launch
   bool transfers = false;
   size_t rcp = 0, amt = 0;
   int wire = 0;
@@ -214,20 +214,46 @@ hipError_t flush_chunk(at2v_ctx* ctx, Shard& s) {
 // Records [a, a + c) of the caller's batch (absolute indices; a multiple of 64 relative to the shard's first record, so
 // the chunk owns whole verdict words): staging slot -> DMA uploads into the chunk's own region of the pipe's device
 // arena -> (the next call of this function, or flush_chunk) verify launch writing d_words (the chunk's words of the
-// shard's device bitmap, zeroed by the launch first). Current device = s.device. The four parts (pk, sig + offsets,
-// messages) are copied and submitted one after the other, so the DMA of one overlaps the host copy of the next; then the
-// previous chunk is launched (its uploads had this chunk's host copy to finish). The first chunk of a call (`first`)
-// is launched at once: it is the pipeline's fill. A slice of pk, sig or msg that lies in pinned memory the context knows
-// (ctx->hostmem) skips the slot: its upload is submitted from the caller's memory, with no host copy. The host waits only
-// for the slot's previous upload (and, when the slot must grow, for its previous launch).
+// shard's device bitmap, zeroed by the launch first) and, where the call asks for them, the recipient_ok words d_rok.
+// Current device = s.device. The chunk's parts are its layout's (at2v_stage_plan.h): pk, sig, rebased offsets and
+// messages of a records call; senders, signatures, recipients and amounts where the call passes fields, whose offsets
+// and messages the prep kernel writes on the device (flush_chunk). A part whose slice lies in pinned memory the context
+// knows (ctx->hostmem: at2v_host_alloc / at2v_host_register) is uploaded from the caller's memory; any other is copied
+// into the slot first, as every slice was before ABI 9. The uploads are staged and submitted one after the other
+// (upload_plan), so the DMA of one overlaps the host copy of the next; then the previous chunk is launched (its uploads
+// had this chunk's host copy to finish). The first chunk of a call (`first`) is launched at once: it is the pipeline's
+// fill. The host waits only for the slot's previous upload (and, when the slot must grow, for its previous launch).
+// The slot's signal counts exactly the uploads that were submitted: when a submit fails, the ones that were never
+// submitted are taken off the count, and the ones in flight still bring it to zero (begin_arena, free_pipe and
+// quiesce_host_calls wait for that), so no upload of a failed call is left uncounted while it may still write the arena
+// or read the caller's memory.
 hipError_t issue_chunk(at2v_ctx* ctx, Shard& s, at2v::CpuPool* copier, const HostBatch& b, size_t a, size_t c,
-                       uint32_t* d_words, bool throughput, bool first) {
+                       uint32_t* d_words, uint32_t* d_rok, bool throughput, bool first) {
   HostPipe& p = *s.pipe;
   const int k = (int)(p.chunks % kStageSlots);
   StageSlot& sl = p.slot[k];
-  const uint32_t mb0 = b.msg_off[a];
-  const size_t mb = (size_t)(b.msg_off[a + c] - mb0);
-  const ChunkLayout L = chunk_layout(c, mb);
+  const size_t mb = b.msg_bytes(a, a + c);
+  const ChunkLayout L = chunk_layout(c, mb, b.transfers);
+  // where the caller holds each part (the built part: the offsets, to rebase by the first one, mb0)
+  const uint8_t* src[at2v::kChunkParts] = {b.pk + a * 32, b.sig + a * 64, nullptr, nullptr};
+  uint32_t mb0 = 0;
+  if (b.transfers) {
+    src[2] = b.recipient + a * 32;
+    src[3] = reinterpret_cast<const uint8_t*>(b.amount + a);
+  } else {
+    mb0 = b.msg_off[a];
+    src[2] = reinterpret_cast<const uint8_t*>(b.msg_off + a);
+    src[3] = mb ? b.msg + mb0 : nullptr;
+  }
+  // per part: the address the DMA engine reads the slice from when it lies wholly inside one known pinned range
+  const uint8_t* dma[at2v::kChunkParts] = {};
+  bool direct[at2v::kChunkParts] = {};
+  for (int i = 0; i < at2v::kChunkParts; ++i) {
+    const at2v::HostRange* r = L.part[i].len && !L.part[i].built ? ctx->hostmem.find(src[i], L.part[i].len) : nullptr;
+    if (r) dma[i] = reinterpret_cast<const uint8_t*>(r->dma + (reinterpret_cast<uintptr_t>(src[i]) - r->base));
+    direct[i] = r != nullptr;
+  }
+  const at2v::UploadPlan plan = at2v::upload_plan(L, direct);
   // (begin_arena sized it by arena_bytes, which bounds every plan's layouts: tests/host/stage_plan_host.cpp)
   if (p.arena_at + L.total > p.arena().cap) return hipErrorInvalidValue;
   uint8_t* d = (uint8_t*)p.arena().p + p.arena_at;
@@ -235,33 +261,17 @@ hipError_t issue_chunk(at2v_ctx* ctx, Shard& s, at2v::CpuPool* copier, const Hos
   using clk = std::chrono::steady_clock;
   const auto t0 = clk::now();
   hipError_t e = wait_uploads(sl);  // (done already: the slot's chunk was launched, which waited for them)
-  if (e == hipSuccess && sl.host_cap < L.total) {
+  if (e == hipSuccess && sl.host_cap < plan.slot_bytes) {
     if (sl.host) (void)hipHostFree(sl.host);
     sl.host = nullptr;
     sl.host_cap = 0;
-    const size_t want = std::max(L.total + L.total / 4, chunk_layout(ctx->stage_max, 0).total);
+    const size_t want = std::max(plan.slot_bytes + plan.slot_bytes / 4, chunk_layout(ctx->stage_max, 0).total);
     e = hipHostMalloc((void**)&sl.host, want, hipHostMallocDefault);
     if (e == hipSuccess) sl.host_cap = want;
   }
   if (e != hipSuccess) return e;
   const auto t1 = clk::now();
-  // Per array: the address the DMA engine reads the chunk's slice from when it lies wholly inside one known pinned range
-  // (at2v_host_alloc / at2v_host_register), else nullptr: the slice is copied into the slot first, as every slice was
-  // before ABI 9. The offsets are always staged (rebased on the host), so a chunk that is direct in all three arrays
-  // still takes its slot, and sig + offsets are two uploads when sig is direct.
-  auto dma_src = [&](const uint8_t* src, size_t len) -> const uint8_t* {
-    const at2v::HostRange* r = ctx->hostmem.find(src, len);
-    return r ? reinterpret_cast<const uint8_t*>(r->dma + (reinterpret_cast<uintptr_t>(src) - r->base)) : nullptr;
-  };
-  const uint8_t* pk_src = dma_src(b.pk + a * 32, c * 32);
-  const uint8_t* sig_src = dma_src(b.sig + a * 64, c * 64);
-  const uint8_t* msg_src = mb ? dma_src(b.msg + mb0, mb) : nullptr;
-  // the uploads submitted below, each decrements the signal when done
-  hsa_signal_store_screlease(sl.uploaded, 1 + (sig_src ? 2 : 1) + (mb ? 1 : 0));
-  auto upload_from = [&](size_t at, const uint8_t* src, size_t len) {
-    return hsa_err(hsa_amd_memory_async_copy(d + at, p.gpu, src, p.cpu, len, 0, nullptr, sl.uploaded));
-  };
-  auto upload = [&](size_t at, size_t len) { return upload_from(at, sl.host + at, len); };
+  hsa_signal_store_screlease(sl.uploaded, plan.count);  // each upload decrements it when done
   // between copy batches: the pending (previous) chunk is launched as soon as its uploads have landed, so the device
   // does not wait for this chunk's whole host copy (the pipeline's fill: the second chunk's launch)
   hipError_t ef = hipSuccess;
@@ -270,131 +280,31 @@ hipError_t issue_chunk(at2v_ctx* ctx, Shard& s, at2v::CpuPool* copier, const Hos
       ef = flush_chunk(ctx, s);
   };
   CopyJob job;
-  if (pk_src) {
-    e = upload_from(0, pk_src, c * 32);
-  } else {
-    job.add(sl.host, b.pk + a * 32, c * 32);
-    run_copy(copier, job, c * 32, poll);
-    e = upload(0, c * 32);
+  const int submitted = at2v::walk_uploads(
+      plan,
+      [&](const at2v::Upload& u) {
+        for (int i = u.part; i < u.part + u.parts; ++i)
+          if (L.part[i].built)
+            job.add_offsets((uint32_t*)(sl.host + L.part[i].at), (const uint32_t*)src[i], c + 1, mb0);
+          else
+            job.add(sl.host + L.part[i].at, src[i], L.part[i].len);
+        run_copy(copier, job, u.len, poll);
+      },
+      [&](const at2v::Upload& u) {
+        return hsa_amd_memory_async_copy(d + u.at, p.gpu, u.direct ? dma[u.part] : sl.host + u.at, p.cpu, u.len, 0,
+                                         nullptr, sl.uploaded) == HSA_STATUS_SUCCESS;
+      });
+  if (submitted < plan.count) {  // the call fails; what was submitted still counts down, what was not never will
+    hsa_signal_subtract_screlease(sl.uploaded, plan.count - submitted);
+    return hipErrorUnknown;
   }
-  if (sig_src) {
-    if (e == hipSuccess) e = upload_from(L.sig, sig_src, c * 64);
-  } else {
-    job.add(sl.host + L.sig, b.sig + a * 64, c * 64);
-  }
-  job.add_offsets((uint32_t*)(sl.host + L.off), b.msg_off + a, c + 1, mb0);
-  run_copy(copier, job, sig_src ? (c + 1) * 4 : c * 68, poll);
-  const size_t off_at = sig_src ? L.off : L.sig;
-  if (e == hipSuccess) e = upload(off_at, L.msg - off_at);
-  if (mb && msg_src) {
-    if (e == hipSuccess) e = upload_from(L.msg, msg_src, mb);
-  } else if (mb) {
-    job.add(sl.host + L.msg, b.msg + mb0, mb);
-    run_copy(copier, job, mb, poll);
-    if (e == hipSuccess) e = upload(L.msg, mb);
-  }
-  const size_t direct = (pk_src ? c * 32 : 0) + (sig_src ? c * 64 : 0) + (msg_src ? mb : 0);
-  ctx->host_direct_bytes += direct;
-  ctx->host_staged_bytes += c * 96 + mb - direct;
-  if (e == hipSuccess) e = ef;
-  if (e != hipSuccess) {  // (a submit failed: nothing waits for this slot's parts any more; the call fails)
-    hsa_signal_store_screlease(sl.uploaded, 0);
-    return e;
-  }
+  ctx->host_direct_bytes += plan.direct_bytes;
+  ctx->host_staged_bytes += plan.staged_bytes;
+  if (ef != hipSuccess) return ef;
   const auto t2 = clk::now();
   e = flush_chunk(ctx, s);
-  p.pend = ChunkLaunch{d, L.sig, L.off, L.msg, mb, c, d_words, throughput, k, (int)(p.chunks % 2)};
-  p.pending = true;
-  if (e == hipSuccess && first) e = flush_chunk(ctx, s);
-  ++p.chunks;
-  ++ctx->host_chunks;
-  if (ctx->pipe_trace) {
-    const auto t3 = clk::now();
-    ctx->tr_wait += std::chrono::duration<double>(t1 - t0).count();
-    ctx->tr_copy += std::chrono::duration<double>(t2 - t1).count();
-    ctx->tr_enq += std::chrono::duration<double>(t3 - t2).count();
-  }
-  return e;
-}
-
-// The same for records [a, a + c) of a transfers call (b.transfers): the chunk is laid out as transfer_layout gives it, and
-// only the four field arrays are uploaded: senders, signatures, recipients and amounts, each straight from a known pinned
-// range or through the staging slot by the rule above, one upload each. Nothing is rebased on the host: the offsets and
-// the messages are written by the prep kernel that flush_chunk launches before the chunk's verify launch, behind the
-// same upload wait. d_rok: the chunk's recipient_ok words of the shard's second bitmap, or null.
-// The slot's signal counts exactly the uploads that were submitted: when a submit fails, the ones that were never
-// submitted are taken off the count, and the ones in flight still bring it to zero (begin_arena and free_pipe wait for
-// that), so no upload of a failed call is left uncounted while it may still write the arena or read the caller's memory.
-hipError_t issue_transfer_chunk(at2v_ctx* ctx, Shard& s, at2v::CpuPool* copier, const HostBatch& b, size_t a, size_t c,
-                                uint32_t* d_words, uint32_t* d_rok, bool throughput, bool first) {
-  HostPipe& p = *s.pipe;
-  const int k = (int)(p.chunks % kStageSlots);
-  StageSlot& sl = p.slot[k];
-  const size_t len = at2v::transfer_msg_len(b.wire);
-  const at2v::TransferLayout L = at2v::transfer_layout(c, len);
-  // (begin_arena sized it by transfer_arena_bytes, which bounds every plan's layouts: tests/host/transfer_plan_host.cpp)
-  if (p.arena_at + L.total > p.arena().cap) return hipErrorInvalidValue;
-  uint8_t* d = (uint8_t*)p.arena().p + p.arena_at;
-  p.arena_at += (L.total + 255) & ~(size_t)255;
-  using clk = std::chrono::steady_clock;
-  const auto t0 = clk::now();
-  hipError_t e = wait_uploads(sl);  // (done already: the slot's chunk was launched, which waited for them)
-  if (e == hipSuccess && sl.host_cap < L.upload) {
-    if (sl.host) (void)hipHostFree(sl.host);
-    sl.host = nullptr;
-    sl.host_cap = 0;
-    const size_t want = std::max(L.upload + L.upload / 4, chunk_layout(ctx->stage_max, 0).total);
-    e = hipHostMalloc((void**)&sl.host, want, hipHostMallocDefault);
-    if (e == hipSuccess) sl.host_cap = want;
-  }
-  if (e != hipSuccess) return e;
-  const auto t1 = clk::now();
-  struct Part {
-    size_t at;
-    const uint8_t* src;
-    size_t len;
-  };
-  const Part parts[4] = {{0, b.pk + a * 32, c * 32},
-                         {L.sig, b.sig + a * 64, c * 64},
-                         {L.rcp, b.recipient + a * 32, c * 32},
-                         {L.amt, reinterpret_cast<const uint8_t*>(b.amount + a), c * 8}};
-  hsa_signal_store_screlease(sl.uploaded, 4);
-  hipError_t ef = hipSuccess;
-  auto poll = [&]() {
-    if (ef == hipSuccess && p.pending && hsa_signal_load_scacquire(p.slot[p.pend.slot].uploaded) == 0)
-      ef = flush_chunk(ctx, s);
-  };
-  CopyJob job;
-  size_t direct = 0;
-  int submitted = 0;
-  for (const Part& pt : parts) {
-    const at2v::HostRange* r = ctx->hostmem.find(pt.src, pt.len);
-    const uint8_t* src = nullptr;
-    if (r) {
-      src = reinterpret_cast<const uint8_t*>(r->dma + (reinterpret_cast<uintptr_t>(pt.src) - r->base));
-      direct += pt.len;
-    } else {
-      job.add(sl.host + pt.at, pt.src, pt.len);
-      run_copy(copier, job, pt.len, poll);
-      src = sl.host + pt.at;
-    }
-    e = hsa_err(hsa_amd_memory_async_copy(d + pt.at, p.gpu, src, p.cpu, pt.len, 0, nullptr, sl.uploaded));
-    if (e != hipSuccess) break;
-    ++submitted;
-  }
-  if (e == hipSuccess) {
-    ctx->host_direct_bytes += direct;
-    ctx->host_staged_bytes += L.upload - direct;
-    e = ef;
-  }
-  if (e != hipSuccess) {  // the call fails; what was submitted still counts down, what was not never will
-    if (submitted < 4) hsa_signal_subtract_screlease(sl.uploaded, 4 - submitted);
-    return e;
-  }
-  const auto t2 = clk::now();
-  e = flush_chunk(ctx, s);
-  p.pend = ChunkLaunch{d, L.sig, L.off, L.msg, c * len, c, d_words, throughput, k, (int)(p.chunks % 2),
-                       true, L.rcp, L.amt, b.wire, d_rok};
+  p.pend = ChunkLaunch{d, L.sig, L.off, L.msg, mb, c, d_words, throughput, k, (int)(p.chunks % 2),
+                       b.transfers, L.rcp, L.amt, b.wire, d_rok};
   p.pending = true;
   if (e == hipSuccess && first) e = flush_chunk(ctx, s);
   ++p.chunks;
@@ -410,15 +320,14 @@ hipError_t issue_transfer_chunk(at2v_ctx* ctx, Shard& s, at2v::CpuPool* copier, 
 
 // The pipe's arena for a shard's part of a call (m records, mb message bytes), before its first chunk: every launch of
 // the previous host-buffer call has completed (the call waited for its verdict copy, which followed them). transfers:
-// the part's chunks are transfer_layouts (mb = m x the message length).
+// the part's chunks are laid out as a transfers call's (mb = m x the message length).
 hipError_t begin_arena(at2v_ctx* ctx, Shard& s, size_t m, size_t mb, bool transfers = false) {
   HostPipe& p = *s.pipe;
   for (StageSlot& sl : p.slot) (void)wait_uploads(sl);  // (after a failed call, uploads may still write the arena)
   p.pending = false;
   p.arena_at = 0;
   const size_t first = std::min(ctx->stage_first, std::max<size_t>(m, 1));
-  return p.arena().ensure(transfers ? at2v::transfer_arena_bytes(m, mb / std::max<size_t>(m, 1), first)
-                                    : at2v::arena_bytes(m, mb, first));
+  return p.arena().ensure(at2v::arena_bytes(m, mb, first, transfers));
 }
 
 at2v::CpuPool* copy_pool(at2v_ctx* ctx) {
@@ -428,15 +337,13 @@ at2v::CpuPool* copy_pool(at2v_ctx* ctx) {
 }
 
 // The next chunk of a shard's part (current device = s.device): the part starts at record lo of the caller's batch b, its
-// verdict words go to d_words. A call over several shards issues their chunks in turn, so every device's pipeline fills
-// early (host_call_issue).
+// verdict words go to d_words (its recipient_ok words to d_rok, or null). A call over several shards issues their chunks
+// in turn, so every device's pipeline fills early (host_call_issue).
 hipError_t issue_next_chunk(at2v_ctx* ctx, Shard& s, at2v::CpuPool* copier, const HostBatch& b, ChunkPlan& cp,
                             size_t lo, uint32_t* d_words, uint32_t* d_rok = nullptr) {
   const size_t at = cp.pos, c = cp.take();
-  if (b.transfers)
-    return issue_transfer_chunk(ctx, s, copier, b, lo + at, c, d_words + at / 32, d_rok ? d_rok + at / 32 : nullptr,
-                                cp.m > ctx->pair_max, at == 0);
-  return issue_chunk(ctx, s, copier, b, lo + at, c, d_words + at / 32, cp.m > ctx->pair_max, at == 0);
+  return issue_chunk(ctx, s, copier, b, lo + at, c, d_words + at / 32, d_rok ? d_rok + at / 32 : nullptr,
+                     cp.m > ctx->pair_max, at == 0);
 }
 
 // stream `st` waits for the shard's last two launches: every chunk issued so far is behind them

@@ -136,6 +136,9 @@ void at2v_destroy(at2v_ctx* ctx);
  *   verdicts ceil(n/32) words out; bit (i % 32) of word (i / 32) = 1 iff record i is valid. Pad bits are 0.
  * Malformed records (undecodable A, s >= l, wrong equation, ...) are verdict 0, never an error; which of those
  * causes it was is answered afterwards by at2v_reject_reasons (below).
+ * The call fails closed: when it was started and does not end in AT2V_OK (a device error without AT2V_CTX_CPU_FALLBACK),
+ * every one of the ceil(n/32) verdict words is 0. An argument error is returned before anything is started and leaves
+ * the words untouched.
  * The library does not retain any pointer after return. n may be 0. n < 2^31. */
 int at2v_verify_batch(at2v_ctx* ctx, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg,
                       const uint32_t* msg_off, size_t n, uint32_t* verdicts);
@@ -147,7 +150,9 @@ int at2v_verify_batch(at2v_ctx* ctx, const uint8_t* pk, const uint8_t* sig, cons
  * at2v_verify_batch_wait(ctx, ticket) has returned; only then are the verdict words final. At most two calls are in
  * flight per context: a submit completes the call two tickets back first (its verdicts land; its result code is lost
  * unless it was waited for). Waiting returns that call's result: AT2V_OK, or the error at2v_verify_batch would have
- * returned (with AT2V_CTX_CPU_FALLBACK the batch is re-verified on the CPU inside the wait). A ticket is waited for
+ * returned (with AT2V_CTX_CPU_FALLBACK the batch is re-verified on the CPU inside the wait). A call that does not end
+ * in AT2V_OK has every verdict word 0, as the synchronous call has, also when a later submit completed it and its code
+ * is lost: words that are all 0 are never a verified batch's. A ticket is waited for
  * once; an unknown, repeated or too old ticket gives AT2V_E_INVALID. at2v_verify_batch and at2v_verify_batch_sharded
  * complete the calls in flight first (their results stay for their waits). Validation errors are returned by the
  * submit (no ticket). */
@@ -274,9 +279,10 @@ int at2v_verify_batch_device(at2v_ctx* ctx, const uint8_t* d_pk, const uint8_t* 
  * straight from a range of at2v_host_alloc / at2v_host_register or through a staging slot by the rule above; all four
  * count in at2v_info.host_direct_bytes / host_staged_bytes, and nothing is rebased on the host. A CPU context verifies on
  * its thread pool with no HIP call. With AT2V_CTX_CPU_FALLBACK a failed device call is verified again on the CPU from the
- * caller's fields, recipient_ok included. These calls fail closed: whenever a call that was started does not end in
- * AT2V_OK, every verdict word and every recipient_ok word of the call is 0, also when a later submit completes it and its
- * result code is lost. (An argument error is returned before anything is started and leaves the outputs untouched.)
+ * caller's fields, recipient_ok included. These calls fail closed as at2v_verify_batch does: whenever a call that was
+ * started does not end in AT2V_OK, every verdict word and every recipient_ok word of the call is 0, also when a later
+ * submit completes it and its result code is lost. (An argument error is returned before anything is started and leaves
+ * the outputs untouched.)
  *
  * at2v_queue_submit_transfers: at2v_queue_submit for n transfers. The messages are built on the host straight into the
  * filling slot's message region; the records get consecutive tickets and everything downstream (poll, reasons, the CPU

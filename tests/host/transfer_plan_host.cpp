@@ -2,16 +2,13 @@
 // UBSan (tests/test_transfer_plan_host.py builds and runs it): a program of its own.
 //   msg     at2v_transfer.h: the signed message of a transfer from (recipient, amount, wire), bytes and words, against
 //           literal bytes for both wires and the amounts 0, 1 and 2^64 - 1; nothing written past the message
-//   plan    at2v_stage_plan.h: every chunk of every plan over m in {1, 63, 64, 65, 4096, 131073, 1000003} for both message
-//           lengths: transfer_layout's parts are 16-byte aligned and disjoint, and the chunks, 256-aligned, fit
-//           transfer_arena_bytes (the inequality issue_transfer_chunk relies on)
-#include <algorithm>
+// (A transfers chunk's layout, uploads and arena bound are checked beside the records form's: stage_plan_host.cpp, tplan.)
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 
-#include "at2v_stage_plan.h"
 #include "at2v_transfer.h"
 
 namespace {
@@ -84,53 +81,11 @@ int run_msg() {
   return 0;
 }
 
-int run_plan() {
-  const size_t ms[] = {1, 63, 64, 65, 4096, 131073, 1000003};
-  const size_t firsts[] = {64, 128, 1024, 65536}, maxes[] = {64, 256, 4096, 131072};
-  const size_t pair_maxes[] = {0, 1, 64, 1000, 2048, 32768};
-  size_t cases = 0, chunks = 0;
-  double tightest = 0;
-  for (size_t stage_first : firsts)
-    for (size_t max_in : maxes) {
-      const size_t stage_max = std::max(max_in, stage_first);  // as at2v_create raises it
-      for (size_t pair_max : pair_maxes)
-        for (size_t m : ms)
-          for (size_t L : {(size_t)48, (size_t)40}) {
-            at2v::ChunkPlan cp;
-            cp.init(m, pair_max, stage_first, stage_max);
-            size_t sum = 0, arena = 0;
-            while (!cp.done()) {
-              const size_t c = cp.take();
-              const at2v::TransferLayout T = at2v::transfer_layout(c, L);
-              if (T.sig % 16 || T.rcp % 16 || T.amt % 16 || T.off % 16 || T.msg % 16)
-                fail("part not 16-byte aligned", c, T.amt, T.off, T.msg);
-              // pk [0, 32c) | sig | recipient | amount [amt, amt + 8c) = upload | offsets (c + 1) | messages c L | 16
-              if (c * 32 > T.sig || T.sig + c * 64 > T.rcp || T.rcp + c * 32 > T.amt || T.amt + c * 8 > T.upload ||
-                  T.upload > T.off || T.off + (c + 1) * 4 > T.msg || T.msg + c * L + 16 != T.total)
-                fail("parts overlap", c, L);
-              if (T.upload != c * at2v::kTransferFieldBytes) fail("upload is not the four field arrays", c, T.upload);
-              if (T.off - T.upload >= 16 || T.msg - (T.off + (c + 1) * 4) >= 16) fail("more padding than alignment needs", c);
-              arena += (T.total + 255) & ~(size_t)255;
-              sum += c;
-              ++chunks;
-            }
-            if (sum != m) fail("chunks do not sum to m", m, sum);
-            const size_t have = at2v::transfer_arena_bytes(m, L, std::min(stage_first, std::max<size_t>(m, 1)));
-            if (arena > have) fail("arena too small", m, L, arena, have);
-            tightest = std::max(tightest, (double)arena / (double)have);
-            ++cases;
-          }
-    }
-  std::printf("cases %zu chunks %zu tightest %.7f\n", cases, chunks, tightest);
-  return 0;
-}
-
 }  // namespace
 
 int main(int argc, char** argv) {
   const char* mode = argc > 1 ? argv[1] : "";
   if (!std::strcmp(mode, "msg")) return run_msg();
-  if (!std::strcmp(mode, "plan")) return run_plan();
-  std::fprintf(stderr, "usage: %s msg | plan\n", argv[0]);
+  std::fprintf(stderr, "usage: %s msg\n", argv[0]);
   return 2;
 }

@@ -203,6 +203,40 @@ def test_cpu_fallback_multi_shard(at2v_mod, oracle, monkeypatch):
         assert np.array_equal(v.verify_batch(pk, sig, msg, off), want)
 
 
+def test_records_call_fails_closed(at2v_mod, golden, monkeypatch):
+    """A records call that was started and fails without AT2V_CTX_CPU_FALLBACK leaves every verdict word 0, as the
+    transfers calls do (AT2V_TEST_FAIL_LAUNCH fails the first verify launch on the host side, before any kernel of it
+    runs): the synchronous call; a submitted call that a later submit completes, whose result code is lost; and a call
+    over eight aliased shards of which one fails while the others' verdict copies ran"""
+    g = golden["adversarial"]
+    words = np.full((g.n + 31) // 32 + 1, 0xFFFFFFFF, np.uint32)
+    monkeypatch.setenv("AT2V_TEST_FAIL_LAUNCH", "1")
+    with at2v_mod.BatchVerifier() as v:
+        with pytest.raises(at2v_mod.At2vError) as ei:
+            v.verify_batch(g.pk, g.sig, g.msg, g.off, words=words[:-1])
+        assert ei.value.code == -3  # AT2V_E_HIP
+        assert not words[:-1].any() and words[-1] == 0xFFFFFFFF
+    with at2v_mod.BatchVerifier() as v:
+        words[:] = 0xFFFFFFFF
+        a = v.submit_batch(g.pk, g.sig, g.msg, g.off, words=words[:-1])
+        b = v.submit_batch(g.pk, g.sig, g.msg, g.off)
+        c = v.submit_batch(g.pk, g.sig, g.msg, g.off)  # completes a
+        assert not words[:-1].any() and words[-1] == 0xFFFFFFFF
+        assert at2v_mod.load_library().at2v_verify_batch_wait(v._h, a.ticket) == -1  # its result is gone
+        assert np.array_equal(v.wait_batch(b), g.dalek) and np.array_equal(v.wait_batch(c), g.dalek)
+    monkeypatch.setenv("AT2V_TEST_DEVICE_ALIAS", "1")
+    g = golden["at2_cfg1"]  # 4,096 records, every one valid: a shard's verdict words that landed would be all ones
+    assert g.n == 4096 and g.dalek.all()
+    words = np.full(g.n // 32 + 1, 0xFFFFFFFF, np.uint32)
+    with at2v_mod.BatchVerifier(num_gpus=8) as v:
+        with pytest.raises(at2v_mod.At2vError) as ei:
+            v.verify_batch(g.pk, g.sig, g.msg, g.off, words=words[:-1])
+        assert ei.value.code < 0
+        assert not words[:-1].any() and words[-1] == 0xFFFFFFFF
+        assert np.array_equal(v.verify_batch(g.pk, g.sig, g.msg, g.off), g.dalek)
+        assert v.info()["cpu_fallbacks"] == 0
+
+
 def test_queue_cpu_fallback(at2v_mod, golden, monkeypatch):
     """AT2V_QUEUE_CPU_FALLBACK: the queue's first two batches fail to launch (test hook); they are verified on the CPU
     from the slots' host records and published in ticket order like every other batch (no 0xff verdicts)"""

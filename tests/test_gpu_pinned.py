@@ -175,6 +175,27 @@ def test_mixed_arrays(at2v_mod, records, chunked):
         assert cnt.delta() == (0, record_bytes(off, N))
 
 
+def test_chunks_with_empty_messages(at2v_mod, oracle, chunked):
+    """4,096 records whose messages are all empty, in three chunks (1,024 / 1,024 / 2,048): a chunk without message bytes
+    has no messages upload (pk, then sig with the offsets; from host_alloc memory pk, sig, then the offsets). Once from
+    pageable arrays and once from one host_alloc range with msg_off[0] = 3; verdicts against the oracle"""
+    n = 4096
+    pk, sig, msg, off, cls = oracle.gen_adversarial(0x9139, 0, n, 0)
+    want = oracle.verify_batch(pk, sig, msg, off)
+    assert msg.size == 0 and 0 < want.sum() < n
+    with at2v_mod.BatchVerifier(small_batch_max=512) as v:
+        cnt = Counters(v)
+        chunks0 = v.info()["host_chunks"]
+        got = v.verify_batch(pk, sig, msg, off)
+        assert np.array_equal(got, want), ("pageable", np.nonzero(got != want)[0][:10])
+        assert cnt.delta() == (0, 96 * n)
+        c = pinned_layout.carve(v.host_alloc(pinned_layout.carved_bytes(n, 0)), pk, sig, msg, off)
+        assert c.msg_bytes == 0 and c.off[0] == 3
+        carved_call(at2v_mod, v, c, want, "host_alloc")
+        assert cnt.delta() == (96 * n, 0)
+        assert v.info()["host_chunks"] - chunks0 == 2 * 3
+
+
 def test_messages_straddling_the_end_of_a_range(at2v_mod, records, chunked):
     """msg registered only up to the middle of the third chunk's messages: the first two chunks' messages go direct, the
     straddling chunk's and every later chunk's are staged; pk and sig are pageable"""

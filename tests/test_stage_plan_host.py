@@ -1,5 +1,5 @@
-"""CPU: the arithmetic of the host-buffer pipeline (csrc/at2v_stage_plan.h: the chunk schedule, a chunk's layout, the
-device arena's size and the copy pieces, which at2v_api_pipe.h's issue_chunk trusts) under AddressSanitizer + UBSan:
+"""CPU: the arithmetic of the host-buffer pipeline (csrc/at2v_stage_plan.h: the chunk schedule, a chunk's layout, its
+uploads, the device arena's size and the copy pieces, which at2v_api_pipe.h's issue_chunk trusts) under ASan + UBSan:
 tests/host/stage_plan_host.cpp, a program of its own. The header includes nothing of HIP, so no GPU is needed."""
 import os
 import subprocess
@@ -52,6 +52,19 @@ def test_chunk_layout_parts(stage_plan_exe):
     """sig, off and msg are 16-byte aligned, pk | sig | offsets | messages do not overlap, upload + 16 == total"""
     got = _run(stage_plan_exe, "layout")
     assert int(got["cases"]) == 600 * 5
+
+
+def test_upload_plan_and_walk(stage_plan_exe):
+    """records and transfers x c in {1, 63, 64, 65, 4096} x message bytes {0, 100 c} x every direct / staged choice of the
+    four parts (for records the offsets' bit must change nothing: they are never read from the caller). The uploads are
+    the sequences written out in the test (pk; sig with the offsets behind it when staged, else sig and then the offsets;
+    the messages if there are any; one upload per field array for transfers), their count is the signal's start value,
+    they are disjoint, inside the uploaded region and cover every part's bytes once, and direct + staged bytes are
+    c * 96 + message bytes (c * 136 for transfers). Then the walk with a submit that fails at every position k (and
+    never): exactly the uploads before k are submitted, nothing after k is staged, and the signal, less the uploads never
+    submitted, counts the ones in flight down to exactly 0"""
+    got = _run(stage_plan_exe, "uploads")
+    assert int(got["cases"]) == 2 * 5 * 2 * 16
 
 
 def test_copy_pieces_cover_their_ranges(stage_plan_exe):

@@ -1,11 +1,13 @@
 """CPU: the HIP-free arithmetic of the transfers entry points (at2v_verify_transfers*) under AddressSanitizer + UBSan:
 tests/host/transfer_plan_host.cpp, a program of its own. csrc/at2v_transfer.h is the one definition of a transfer's signed
 message from its fields (the prep kernel, the CPU backend and the ingest queue all use it); csrc/at2v_stage_plan.h lays a
-transfers chunk out on the device and bounds the arena, which at2v_api_pipe.h's issue_transfer_chunk trusts."""
+transfers chunk out on the device and bounds the arena, which at2v_api_pipe.h's issue_chunk trusts: that part runs in
+tests/host/stage_plan_host.cpp, beside the records form over the same layout code."""
 import os
 import subprocess
 
 import pytest
+from test_stage_plan_host import stage_plan_exe  # noqa: F401  (the fixture that builds stage_plan_host.cpp)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "at2-node_amd", "csrc")
@@ -46,11 +48,12 @@ def test_message_builder_against_literal_bytes(transfer_plan_exe):
     assert int(got["cases"]) == 4 * 2
 
 
-def test_transfer_chunks_fit_their_arena(transfer_plan_exe):
+def test_transfer_chunks_fit_their_arena(stage_plan_exe):  # noqa: F811
     """stage_first {64, 128, 1024, 65536} x stage_max {64, 256, 4096, 131072} (raised to stage_first) x small_batch_max
     {0, 1, 64, 1000, 2048, 32768} x m in {1, 63, 64, 65, 4096, 131073, 1000003} x message length {48, 40}: every
-    chunk's transfer_layout has 16-byte-aligned, disjoint parts with no more padding than alignment needs, uploads exactly
-    136 bytes per record, and the chunks, 256-aligned, fit transfer_arena_bytes(m, L, min(stage_first, max(m, 1)))"""
-    got = _run(transfer_plan_exe, "plan")
+    chunk's layout has 16-byte-aligned, disjoint parts with no more padding than alignment needs, uploads exactly
+    136 bytes per record, and the chunks, 256-aligned, fit arena_bytes(m, m L, min(stage_first, max(m, 1)), transfers);
+    the chunks also keep the size rules of the records plan"""
+    got = _run(stage_plan_exe, "tplan")
     assert int(got["cases"]) == 4 * 4 * 6 * 7 * 2
     assert 0.5 < float(got["tightest"]) <= 1.0, got

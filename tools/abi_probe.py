@@ -8,8 +8,10 @@ single-thread numpy copy rate of the batch (host memory bandwidth).
 at2v_host_alloc (uploaded straight from there, no staging copy); the two forms alternate within a round (pageable first
 in even rounds, pinned first in odd ones). Both are printed in ms per call and as a fraction of the device-API kernel
 time measured in this process; the JSON has the pinned form under "<variant>+pinned".
+--transfers: a third form per round, at2v_verify_transfers over the pageable fields of n valid transfers with 48-byte
+messages (signed on the GPU, as tools/transfers_probe.py makes them); in the JSON under "<variant>+transfers".
 usage: python tools/abi_probe.py [--n 1048576] [--calls 8] [--rounds 2] [--variants first:max:threads[:streams],...]
-       [--pinned] [--trace]
+       [--pinned] [--transfers] [--trace]
 -> one JSON line"""
 import argparse
 import json
@@ -29,6 +31,7 @@ def main():
     ap.add_argument("--msg-len", type=int, default=100)
     ap.add_argument("--variants", default="32768:131072:8")
     ap.add_argument("--pinned", action="store_true", help="also run every variant from at2v_host_alloc memory")
+    ap.add_argument("--transfers", action="store_true", help="also run at2v_verify_transfers from pageable fields")
     ap.add_argument("--trace", action="store_true", help="AT2V_TEST_PIPE_TRACE: the host's time per call, on stderr")
     ap.add_argument("--host-only", action="store_true", help="skip the device-API timings (for kernel traces)")
     ap.add_argument("--lib", default="", help="a libat2v variant (tools/build_variant.sh) instead of the product")
@@ -120,6 +123,10 @@ def main():
     print(f"[abi_probe] device-API kernel after an idle gap (ms -> ms): {gaps}", file=sys.stderr, flush=True)
     pk, sig, msg = d_pk.cpu().numpy(), d_sig.cpu().numpy(), d_msg.cpu().numpy()
     off = d_off.cpu().numpy().view(np.uint32)
+    fields = None
+    if a.transfers:
+        from transfers_probe import make_transfers
+        fields = make_transfers(g, n, 0, np.random.default_rng(0x7A5F))[:4]  # sender, sig, recipient, amount
     g.close()
     tmp = np.empty(n * (96 + L), np.uint8)
     src = np.concatenate([pk, sig, msg])
@@ -135,7 +142,7 @@ def main():
             os.environ["AT2V_TEST_STAGE_FIRST"] = first
             os.environ["AT2V_TEST_STAGE_MAX"] = mx
             os.environ["AT2V_TEST_COPY_THREADS"] = th
-            forms = ("pageable", "pinned") if a.pinned else ("pageable",)
+            forms = ("pageable",) + (("pinned",) if a.pinned else ()) + (("transfers",) if a.transfers else ())
             for form in forms[::-1] if r % 2 else forms:
                 v = at2v.BatchVerifier()
                 lib = v._lib
@@ -151,18 +158,27 @@ def main():
                 else:
                     c_pk, c_sig, c_msg, c_words = pk, sig, msg, words
                 c_words[:] = 0
-                ptrs = (c_pk.ctypes.data, c_sig.ctypes.data, c_msg.ctypes.data, off.ctypes.data)
+                if form == "transfers":
+                    ptrs = tuple(x.ctypes.data for x in fields)
+
+                    def call():
+                        return lib.at2v_verify_transfers(v._h, *ptrs, n, at2v.WIRE_BYTES, c_words.ctypes.data, None)
+                else:
+                    ptrs = (c_pk.ctypes.data, c_sig.ctypes.data, c_msg.ctypes.data, off.ctypes.data)
+
+                    def call():
+                        return lib.at2v_verify_batch(v._h, *ptrs, n, c_words.ctypes.data)
                 print(f"[abi_probe] round {r} {var} {form}: {a.calls + 1} calls", file=sys.stderr, flush=True)
-                assert lib.at2v_verify_batch(v._h, *ptrs, n, c_words.ctypes.data) == 0
+                assert call() == 0
                 times = []
                 for _ in range(a.calls):
                     t0 = time.perf_counter()
-                    assert lib.at2v_verify_batch(v._h, *ptrs, n, c_words.ctypes.data) == 0
+                    assert call() == 0
                     times.append((time.perf_counter() - t0) * 1e3)
                 ok = bool((c_words[: n // 32] == 0xFFFFFFFF).all())
                 inf = v.info()
                 v.close()
-                key = var if form == "pageable" else var + "+pinned"
+                key = var if form == "pageable" else var + "+" + form
                 d = out["variants"].setdefault(key, {"ms": [], "ok": True})
                 d["ms"].append(sorted(times)[len(times) // 2])
                 d["ok"] &= ok
