@@ -25,15 +25,19 @@ LIB_PATH = os.path.join(_HERE, "libat2v.so")
 
 POLICY_DALEK_V1 = 0
 POLICY_LIBSODIUM_1_0_18 = 1
+POLICY_DALEK_V1_LEGACY = 2  # dalek built with `legacy_compatibility`: V1 is "the three top bits of S clear", s unreduced
 _POLICIES = {"dalek": POLICY_DALEK_V1, "dalek_v1": POLICY_DALEK_V1, "libsodium": POLICY_LIBSODIUM_1_0_18,
-             "libsodium_1_0_18": POLICY_LIBSODIUM_1_0_18, POLICY_DALEK_V1: POLICY_DALEK_V1,
-             POLICY_LIBSODIUM_1_0_18: POLICY_LIBSODIUM_1_0_18}
+             "libsodium_1_0_18": POLICY_LIBSODIUM_1_0_18, "dalek-legacy": POLICY_DALEK_V1_LEGACY,
+             "dalek_v1_legacy": POLICY_DALEK_V1_LEGACY, POLICY_DALEK_V1: POLICY_DALEK_V1,
+             POLICY_LIBSODIUM_1_0_18: POLICY_LIBSODIUM_1_0_18, POLICY_DALEK_V1_LEGACY: POLICY_DALEK_V1_LEGACY}
+# include/at2v.h AT2V_MASK_*: bit p of a policy-mask byte is set iff policy p accepts the record
+MASK_DALEK_V1, MASK_LIBSODIUM, MASK_DALEK_V1_LEGACY = 1, 2, 4
 
 # must match include/at2v.h (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = ("at2v_abi_version", "at2v_create", "at2v_destroy", "at2v_verify_batch", "at2v_verify_batch_device",
                     "at2v_verify_one", "at2v_verify_one_policy", "at2v_strerror", "at2v_gen_records_device",
                     "at2v_reject_reasons", "at2v_reject_reasons_device", "at2v_verify_one_reason", "at2v_reason_name",
-                    "at2v_queue_poll_reasons",
+                    "at2v_queue_poll_reasons", "at2v_policy_mask", "at2v_policy_mask_device",
                     "at2v_gen_records_senders_device", "at2v_gen_records_keys_device", "at2v_sign_batch", "at2v_get_info", "at2v_decode_points",
                     "at2v_comm_get_unique_id", "at2v_comm_init_rank", "at2v_verify_shard_gather_device",
                     "at2v_verify_batch_sharded", "at2v_verify_batch_submit", "at2v_verify_batch_wait",
@@ -47,6 +51,23 @@ EXPORTED_SYMBOLS = ("at2v_abi_version", "at2v_create", "at2v_destroy", "at2v_ver
                     "at2v_ledger_create", "at2v_ledger_destroy", "at2v_ledger_balance", "at2v_ledger_last_sequence",
                     "at2v_ledger_transfer", "at2v_ledger_recent_put", "at2v_ledger_recent_get",
                     "at2v_ledger_deliver", "at2v_ledger_pending")
+
+
+def _second_pass_args(pk, sig, verdict_words):
+    """pk, sig and the verdict words (uint32 words, or bool[n] verdicts) of a pass that follows a verify call"""
+    pk = np.ascontiguousarray(pk, dtype=np.uint8)
+    sig = np.ascontiguousarray(sig, dtype=np.uint8)
+    n = pk.size // 32
+    w = np.asarray(verdict_words)
+    if w.dtype == bool:
+        if w.shape != (n,):
+            raise ValueError("bool verdicts must have one entry per record")
+        b = np.packbits(w.astype(np.uint8), bitorder="little")
+        w = np.concatenate([b, np.zeros((-len(b)) % 4, np.uint8)]).view("<u4")
+    words = np.ascontiguousarray(w, dtype=np.uint32).reshape(-1)
+    if pk.size != 32 * n or sig.size != 64 * n or words.size < (n + 31) // 32:
+        raise ValueError("pk/sig/verdict_words sizes disagree")
+    return pk, sig, n, words
 
 
 class At2vError(RuntimeError):
@@ -226,6 +247,10 @@ def _load(path: str) -> ctypes.CDLL:
     lib.at2v_reject_reasons.restype = ctypes.c_int
     lib.at2v_reject_reasons_device.argtypes = [P, P, P, ctypes.c_size_t, P, P, P]
     lib.at2v_reject_reasons_device.restype = ctypes.c_int
+    lib.at2v_policy_mask.argtypes = [P, P, P, ctypes.c_size_t, P, P]
+    lib.at2v_policy_mask.restype = ctypes.c_int
+    lib.at2v_policy_mask_device.argtypes = [P, P, P, ctypes.c_size_t, P, P, P]
+    lib.at2v_policy_mask_device.restype = ctypes.c_int
     lib.at2v_verify_one_reason.argtypes = [P, P, P, ctypes.c_size_t, ctypes.c_int]
     lib.at2v_verify_one_reason.restype = ctypes.c_int
     lib.at2v_reason_name.argtypes = [ctypes.c_int]
@@ -607,18 +632,7 @@ class BatchVerifier:
         """host arrays and the verdict words of a verify call over them (uint32, ceil(n/32); or bool[n] verdicts) ->
         u8[n] at2v_reason per record: 0 where the verdict bit is set, else the first failing check (REASON_*). The pass
         does not re-verify. A failed call raises; the library has then filled every byte with REASON_UNKNOWN."""
-        pk = np.ascontiguousarray(pk, dtype=np.uint8)
-        sig = np.ascontiguousarray(sig, dtype=np.uint8)
-        n = pk.size // 32
-        w = np.asarray(verdict_words)
-        if w.dtype == bool:
-            if w.shape != (n,):
-                raise ValueError("bool verdicts must have one entry per record")
-            b = np.packbits(w.astype(np.uint8), bitorder="little")
-            w = np.concatenate([b, np.zeros((-len(b)) % 4, np.uint8)]).view("<u4")
-        words = np.ascontiguousarray(w, dtype=np.uint32).reshape(-1)
-        if pk.size != 32 * n or sig.size != 64 * n or words.size < (n + 31) // 32:
-            raise ValueError("pk/sig/verdict_words sizes disagree")
+        pk, sig, n, words = _second_pass_args(pk, sig, verdict_words)
         reasons = np.full(max(1, n), REASON_UNKNOWN, np.uint8)
         _check(self._lib.at2v_reject_reasons(self._h, _ptr(pk), _ptr(sig), n, _ptr(words), _ptr(reasons)),
                "at2v_reject_reasons")
@@ -630,6 +644,22 @@ class BatchVerifier:
         its d_pk, d_sig and d_verdicts; d_reasons receives n bytes (16-byte aligned)"""
         _check(self._lib.at2v_reject_reasons_device(self._h, d_pk, d_sig, n, d_verdicts, d_reasons, stream or None),
                "at2v_reject_reasons_device")
+
+    def policy_mask(self, pk: np.ndarray, sig: np.ndarray, verdict_words: np.ndarray) -> np.ndarray:
+        """host arrays and the verdict words of a verify call over them by THIS verifier, which must have been created
+        with policy="dalek-legacy" (uint32, ceil(n/32); or bool[n] verdicts) -> u8[n]: bit p set iff policy p accepts the
+        record (MASK_*; 0, 4, 5 or 7). The pass does not re-verify. A failed call raises; the library has then filled
+        every byte with 0 (a verifier of another policy is refused and nothing is written)."""
+        pk, sig, n, words = _second_pass_args(pk, sig, verdict_words)
+        mask = np.zeros(max(1, n), np.uint8)
+        _check(self._lib.at2v_policy_mask(self._h, _ptr(pk), _ptr(sig), n, _ptr(words), _ptr(mask)), "at2v_policy_mask")
+        return mask[:n]
+
+    def policy_mask_device(self, d_pk: int, d_sig: int, n: int, d_verdicts: int, d_mask: int, stream: int = 0) -> None:
+        """device pointers, asynchronous on `stream`: enqueue right after verify_batch_device on the same stream with
+        its d_pk, d_sig and d_verdicts (policy="dalek-legacy" only); d_mask receives n bytes (16-byte aligned)"""
+        _check(self._lib.at2v_policy_mask_device(self._h, d_pk, d_sig, n, d_verdicts, d_mask, stream or None),
+               "at2v_policy_mask_device")
 
     def sign_batch(self, seeds: np.ndarray, msg: np.ndarray, msg_off: np.ndarray):
         seeds = np.ascontiguousarray(seeds, dtype=np.uint8)

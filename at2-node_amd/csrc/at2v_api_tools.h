@@ -1,5 +1,6 @@
 // at2v_api_tools.h — the entry points beside the verify path: the record generator, the signer, point decoding and the
-// reject reasons (part of the one translation unit at2v_api.hip). Each works on the context's first shard.
+// reject reasons and the policy mask (part of the one translation unit at2v_api.hip). Each works on the context's first
+// shard.
 #pragma once
 #include "at2v_api_ctx.h"
 #include "at2v_reason_launch.h"
@@ -34,6 +35,39 @@ hipError_t launch_reasons(at2v_ctx* ctx, const uint8_t* d_pk, const uint8_t* d_s
   }
   if (!at2v::launch_reject_reasons) return hipErrorNoBinaryForGpu;  // linked without at2v_reason.o (a weak symbol)
   return at2v::launch_reject_reasons(d_pk, d_sig, (uint32_t)n, d_verdicts, d_reasons, (int)ctx->policy, stream);
+}
+
+// The policy-mask launch of a context, as launch_reasons: no scratch set, no event, no sender cache.
+hipError_t launch_mask(at2v_ctx* ctx, const uint8_t* d_pk, const uint8_t* d_sig, size_t n, const uint32_t* d_verdicts,
+                       uint8_t* d_mask, hipStream_t stream) {
+  if (ctx->test_fail_launches) {
+    --ctx->test_fail_launches;
+    return hipErrorLaunchFailure;
+  }
+  if (!at2v::launch_policy_mask) return hipErrorNoBinaryForGpu;  // linked without at2v_reason.o (a weak symbol)
+  return at2v::launch_policy_mask(d_pk, d_sig, (uint32_t)n, d_verdicts, d_mask, stream);
+}
+
+// The host form on a GPU context: every record travels (an accepted record's mask depends on its bytes, a rejected one's
+// is 0), with the caller's verdict words; the n bytes come back into `mask`.
+hipError_t mask_of_records(at2v_ctx* ctx, Shard& s, const uint8_t* pk, const uint8_t* sig, size_t n,
+                           const uint32_t* verdicts, uint8_t* mask) {
+  const size_t words = (n + 31) / 32;
+  const DeviceScope scope(s.device);
+  hipError_t e = scope.err;
+  if (e == hipSuccess) e = s.pk.ensure(n * 32);
+  if (e == hipSuccess) e = s.sig.ensure(n * 64);
+  if (e == hipSuccess) e = s.verdict.ensure(words * 4);
+  if (e == hipSuccess) e = s.reasons.ensure(n);
+  if (e == hipSuccess) e = hipMemcpyAsync(s.pk.p, pk, n * 32, hipMemcpyHostToDevice, s.stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(s.sig.p, sig, n * 64, hipMemcpyHostToDevice, s.stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(s.verdict.p, verdicts, words * 4, hipMemcpyHostToDevice, s.stream);
+  if (e == hipSuccess)
+    e = launch_mask(ctx, (const uint8_t*)s.pk.p, (const uint8_t*)s.sig.p, n, (const uint32_t*)s.verdict.p,
+                    (uint8_t*)s.reasons.p, s.stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(mask, s.reasons.p, n, hipMemcpyDeviceToHost, s.stream);
+  const hipError_t es = s.stream ? hipStreamSynchronize(s.stream) : hipSuccess;  // (also after an error)
+  return e != hipSuccess ? e : es;
 }
 
 // The host form on a GPU context: only the m rejected records (idx, ascending) go to the device, with an all-zero
@@ -194,5 +228,41 @@ int at2v_reject_reasons(at2v_ctx* ctx, const uint8_t* pk, const uint8_t* sig, si
     return AT2V_OK;
   }
   std::memset(reasons, AT2V_REASON_UNKNOWN, n);  // fail closed
+  return rc;
+}
+
+int at2v_policy_mask_device(at2v_ctx* ctx, const uint8_t* d_pk, const uint8_t* d_sig, size_t n,
+                            const uint32_t* d_verdicts, uint8_t* d_mask, void* hip_stream) {
+  if (!ctx || ctx->policy != AT2V_POLICY_DALEK_V1_LEGACY) return AT2V_E_INVALID;
+  if (n == 0) return AT2V_OK;
+  if (!d_pk || !d_sig || !d_verdicts || !d_mask || n >= (1u << 31)) return AT2V_E_INVALID;
+  if (ctx->shards.empty()) return AT2V_E_NODEVICE;
+  if (!aligned(d_pk, 16) || !aligned(d_sig, 16) || !aligned(d_verdicts, 4) || !aligned(d_mask, 16)) return AT2V_E_ALIGN;
+  const DeviceScope scope(ctx->shards[0].device);
+  hipError_t e = scope.err;
+  if (e == hipSuccess) e = launch_mask(ctx, d_pk, d_sig, n, d_verdicts, d_mask, (hipStream_t)hip_stream);
+  return hip_code(e);
+}
+
+int at2v_policy_mask(at2v_ctx* ctx, const uint8_t* pk, const uint8_t* sig, size_t n, const uint32_t* verdicts,
+                     uint8_t* mask) {
+  if (!ctx || ctx->policy != AT2V_POLICY_DALEK_V1_LEGACY) return AT2V_E_INVALID;  // nothing written
+  if (n == 0) return AT2V_OK;
+  if (!mask || n >= (1u << 31)) return AT2V_E_INVALID;
+  if (!pk || !sig || !verdicts) {
+    std::memset(mask, 0, n);
+    return AT2V_E_INVALID;
+  }
+  if (ctx->shards.empty()) {  // CPU context: the same routine over its thread pool
+    at2v::cpu_policy_mask(ctx->cpu, pk, sig, n, verdicts, mask);
+    return AT2V_OK;
+  }
+  const int rc = hip_code(mask_of_records(ctx, ctx->shards[0], pk, sig, n, verdicts, mask));
+  if (rc == AT2V_OK) return AT2V_OK;
+  if (ctx->cpu) {  // AT2V_CTX_CPU_FALLBACK: the records are still on the host
+    at2v::cpu_policy_mask(ctx->cpu, pk, sig, n, verdicts, mask);
+    return AT2V_OK;
+  }
+  std::memset(mask, 0, n);  // fail closed: no policy accepts
   return rc;
 }

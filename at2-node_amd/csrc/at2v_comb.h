@@ -126,7 +126,7 @@ AT2V_HD AT2V_INLINE int gu_encode_eq_zi(const P& p, const fu& zi, const uint32_t
 // Checks that need no point arithmetic: V1 (s < l), A's decode verdict (held with the comb), libsodium's pre-rejects.
 AT2V_HD AT2V_INLINE int comb_prechecks(const uint32_t Rw[8], const uint32_t Aw[8], const uint32_t Sw[8], int policy,
                                        int a_ok) {
-  int ok = sc_is_canonical(Sw) & a_ok;
+  int ok = sc_v1_ok(Sw, policy) & a_ok;
   if (policy == POLICY_LIBSODIUM_1_0_18) {
     ok &= !enc_small_order(Rw);
     ok &= enc_y_canonical(Aw) & !enc_small_order(Aw);

@@ -51,6 +51,11 @@ void cpu_sender_status(CpuPool* p, const uint8_t* pk, size_t n, uint8_t* status)
 void cpu_reject_reasons(CpuPool* p, const uint8_t* pk, const uint8_t* sig, size_t n, const uint32_t* verdict_words,
                         int policy, uint8_t* reasons);
 
+// mask[i] = the AT2V_MASK_* bits of record i (at2v_reason.h policy_mask; 0 where bit i of verdict_words, the verdicts of
+// a verify under AT2V_POLICY_DALEK_V1_LEGACY, is clear), n bytes, synchronous. Chunks of 64 records own their bytes.
+void cpu_policy_mask(CpuPool* p, const uint8_t* pk, const uint8_t* sig, size_t n, const uint32_t* verdict_words,
+                     uint8_t* mask);
+
 // One record through the joint-table form of the verify routine (verify_half_fu_joint, what the GPU's verify_kernel
 // runs) with the host tables: the verdict at2v_verify_one_policy gives, 0 or 1. For tests (tests/host/joint_host.cpp);
 // not part of the ABI. Arguments as at2v_verify_one_policy's, already checked.

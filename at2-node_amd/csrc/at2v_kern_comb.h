@@ -104,7 +104,7 @@ __global__ __launch_bounds__(kLatBlock, 1) void verify_comb_lat_kernel(
         gu_p3 P;
         gu_p3_identity(P);
         if (w == 1) {
-          sok[lane] = (uint32_t)sc_is_canonical(Sw);
+          sok[lane] = (uint32_t)sc_v1_ok(Sw, policy);
           uint32_t sd[kBCombLatDigitWords];
           bcomb_recode<kBCombLatBits>(sd, Sw);
           const DevBCombLat tb{c.bcomb_lat, {st0, st1}, lane};

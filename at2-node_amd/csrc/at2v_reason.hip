@@ -1,5 +1,6 @@
 // at2v_reason.hip — the reject-reasons pass on the device (include/at2v.h at2v_reject_reasons_device): for every record
-// whose verdict bit is 0, which check failed (at2v_reason.h reject_reason). Its own translation unit and code object:
+// whose verdict bit is 0, which check failed (at2v_reason.h reject_reason); and, at the end of the file, the policy-mask
+// pass (at2v_policy_mask_device): for every record, which policies accept it. Its own translation unit and code object:
 // nothing here is seen by the verify kernels (at2v_kernels.hip), whose object does not depend on this file.
 //
 // Rejected records are usually few (10 % in the adversarial mix) but spread, so that almost every wave of 64 holds one:
@@ -75,6 +76,46 @@ hipError_t launch_reject_reasons(const uint8_t* pk, const uint8_t* sig, uint32_t
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(reject_reason_kernel, dim3((n + kReasonTile - 1) / kReasonTile), dim3(kReasonBlock), 0, stream,
                      pk, sig, n, verdict_words, reasons, policy);
+  return hipGetLastError();
+}
+
+// The policy-mask pass (include/at2v.h at2v_policy_mask_device; at2v_reason.h policy_mask): one lane per record, no
+// decode and no field arithmetic, so nothing to compact. A block owns kMaskBlock consecutive records and their bytes,
+// assembles them in LDS (0 for a rejected record, whose 96 bytes are not read) and writes them once, 16 bytes per lane;
+// the last block's tail goes out byte by byte. No global byte is stored twice, none at or after mask + n.
+constexpr int kMaskBlock = 256;
+static_assert(kMaskBlock % 64 == 0, "whole waves of whole verdict words; every block's bytes start 16-byte aligned");
+
+__global__ __launch_bounds__(kMaskBlock) void policy_mask_kernel(
+    const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig, uint32_t n,
+    const uint32_t* __restrict__ verdict_words, uint8_t* __restrict__ mask) {
+  __shared__ uint4 bytes16[kMaskBlock / 16];
+  uint8_t* const bytes = reinterpret_cast<uint8_t*>(bytes16);
+  const uint32_t tid = threadIdx.x;
+  const uint32_t tile0 = blockIdx.x * kMaskBlock;  // < n < 2^31
+  const uint32_t i = tile0 + tid;
+  uint8_t b = 0;
+  if (i < n && ((verdict_words[i >> 5] >> (i & 31)) & 1u)) {
+    uint32_t Aw[8], Rw[8], Sw[8];
+    reason_load8(Aw, pk + (size_t)i * 32);
+    reason_load8(Rw, sig + (size_t)i * 64);
+    reason_load8(Sw, sig + (size_t)i * 64 + 32);
+    b = (uint8_t)policy_mask(Aw, Rw, Sw, 1);
+  }
+  bytes[tid] = b;
+  __syncthreads();
+  const uint32_t m = n - tile0 < kMaskBlock ? n - tile0 : kMaskBlock;  // the block's records
+  uint8_t* const out = mask + tile0;
+  if (tid < m / 16) reinterpret_cast<uint4*>(out)[tid] = bytes16[tid];
+  const uint32_t t = (m & ~15u) + tid;
+  if (t < m) out[t] = bytes[t];
+}
+
+hipError_t launch_policy_mask(const uint8_t* pk, const uint8_t* sig, uint32_t n, const uint32_t* verdict_words,
+                              uint8_t* mask, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(policy_mask_kernel, dim3((n + kMaskBlock - 1) / kMaskBlock), dim3(kMaskBlock), 0, stream, pk, sig,
+                     n, verdict_words, mask);
   return hipGetLastError();
 }
 

@@ -16,4 +16,9 @@ __attribute__((weak)) hipError_t launch_reject_reasons(const uint8_t* pk, const 
                                                        const uint32_t* verdict_words, uint8_t* reasons, int policy,
                                                        hipStream_t stream);
 
+// mask[i] = the AT2V_MASK_* bits of record i for i < n (0 where bit i of verdict_words, the verdicts of a verify under
+// the LEGACY policy, is clear), asynchronous on `stream`. Alignment, n and the bytes written as above; weak likewise.
+__attribute__((weak)) hipError_t launch_policy_mask(const uint8_t* pk, const uint8_t* sig, uint32_t n,
+                                                    const uint32_t* verdict_words, uint8_t* mask, hipStream_t stream);
+
 }  // namespace at2v

@@ -1,5 +1,6 @@
 // at2v_sc.h — scalars mod l = 2^252 + 27742317777372353535851937790883648493 (8 x u32, little-endian).
 //   sc_is_canonical : V1, s < l (dalek check_scalar / from_canonical_bytes)
+//   sc_v1_ok        : V1 under a policy (the legacy rule: s < 2^253)
 //   sc_reduce512    : V3, k = LE512(SHA-512(R||A||M)) mod l (Barrett, HAC 14.42, base 2^32)
 //   sc_recode4/8    : signed fixed-window digits for the wavefront-uniform ladder
 #pragma once
@@ -19,6 +20,17 @@ AT2V_HD AT2V_INLINE int sc_is_canonical(const uint32_t s[8]) {
     borrow = (d >> 63) & 1;
   }
   return (int)borrow;
+}
+
+// Verdict semantics (include/at2v.h at2v_policy).
+enum { POLICY_DALEK_V1 = 0, POLICY_LIBSODIUM_1_0_18 = 1, POLICY_DALEK_V1_LEGACY = 2 };
+
+// V1 under `policy` (uniform over a launch): s < l, or under dalek's legacy_compatibility rule only the three top bits
+// of S clear (s < 2^253), s then being used unreduced. Everything downstream takes any s < 2^253: sc_mul_signed reduces
+// the 512-bit product c1 s, and the radix-2^W recodings (sc_recode8 / 16 / _w) cover ceil(254/W) W >= 254 bits with a
+// top digit < 2^13 + 1, so no carry leaves it.
+AT2V_HD AT2V_INLINE int sc_v1_ok(const uint32_t s[8], int policy) {
+  return policy == POLICY_DALEK_V1_LEGACY ? (int)((s[7] >> 29) == 0u) : sc_is_canonical(s);
 }
 
 // r (9 words) -= l when r >= l

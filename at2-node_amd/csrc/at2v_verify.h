@@ -39,8 +39,6 @@
 
 namespace at2v {
 
-enum { POLICY_DALEK_V1 = 0, POLICY_LIBSODIUM_1_0_18 = 1 };
-
 // uniform-index select from an N-word register array (avoids scratch for a runtime index)
 template <int N>
 AT2V_HD AT2V_INLINE uint32_t seln(const uint32_t* w, int j) {
@@ -110,8 +108,8 @@ AT2V_HD AT2V_INLINE void ge_scalarmult_base(ge_p2& out, const uint32_t s[8], con
 template <int WB, class TabA, class TabB, class MsgWord>
 AT2V_HD AT2V_INLINE int verify_ladder(ge_p2& Rp, const uint32_t Rw[8], const uint32_t Aw[8], const uint32_t Sw[8],
                                       uint32_t len, MsgWord msgword, int policy, TabA& ta, const TabB& tb) {
-  // V1: s < l
-  int ok = sc_is_canonical(Sw);
+  // V1: s < l (legacy policy: s < 2^253)
+  int ok = sc_v1_ok(Sw, policy);
   if (policy == POLICY_LIBSODIUM_1_0_18) {
     ok &= !enc_small_order(Rw);
     ok &= enc_y_canonical(Aw) & !enc_small_order(Aw);
@@ -260,8 +258,8 @@ template <class TabP, class TabB0, class TabB1, class MsgWord, class WaveMax, cl
 AT2V_HD AT2V_INLINE int verify_half(const uint32_t Rw[8], const uint32_t Aw[8], const uint32_t Sw[8], uint32_t len,
                                     MsgWord msgword, int policy, TabP& ta, TabP& tr, const TabB0& tb0,
                                     const TabB1& tb1, WaveMax wave_max, Pace&& pace = Pace()) {
-  // V1: s < l
-  int ok = sc_is_canonical(Sw);
+  // V1: s < l (legacy policy: s < 2^253)
+  int ok = sc_v1_ok(Sw, policy);
   if (policy == POLICY_LIBSODIUM_1_0_18) {
     ok &= !enc_small_order(Rw);
     ok &= enc_y_canonical(Aw) & !enc_small_order(Aw);

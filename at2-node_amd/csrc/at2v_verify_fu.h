@@ -103,7 +103,7 @@ AT2V_HD AT2V_INLINE int verify_half_fu(const uint32_t Rw[8], const uint32_t Aw[8
                                        const TabB1& tb1, WaveMax wave_max, Pace&& pace = Pace(), int a_cached = 0,
                                        int a_cached_ok = 0) {
   // V1: s < l
-  int ok = sc_is_canonical(Sw);
+  int ok = sc_v1_ok(Sw, policy);
   if (policy == POLICY_LIBSODIUM_1_0_18) {
     ok &= !enc_small_order(Rw);
     ok &= enc_y_canonical(Aw) & !enc_small_order(Aw);
@@ -518,7 +518,7 @@ AT2V_HD AT2V_INLINE int verify_half_fu_joint(const uint32_t Rw[8], const uint32_
                                              uint32_t len, MsgWord msgword, int policy, TabJ& tj, const TabB0& tb0,
                                              const TabB1& tb1, WaveMax wave_max, Pace&& pace = Pace()) {
   // V1: s < l
-  int ok = sc_is_canonical(Sw);
+  int ok = sc_v1_ok(Sw, policy);
   if (policy == POLICY_LIBSODIUM_1_0_18) {
     ok &= !enc_small_order(Rw);
     ok &= enc_y_canonical(Aw) & !enc_small_order(Aw);
@@ -682,7 +682,7 @@ AT2V_HD AT2V_INLINE int verify_pair_part(int side, const uint32_t Rw[8], const u
   int ok;
   gu_p3 P;
   if (side == 0) {
-    ok = sc_is_canonical(Sw);
+    ok = sc_v1_ok(Sw, policy);
     if (policy == POLICY_LIBSODIUM_1_0_18) {
       ok &= !enc_small_order(Rw);
       ok &= enc_y_canonical(Aw) & !enc_small_order(Aw);
@@ -838,7 +838,7 @@ AT2V_HD AT2V_INLINE void split_side_ladder(gu_p3& out, const uint32_t cd[8], int
 template <class TabP>
 AT2V_HD AT2V_INLINE int split_a_side(gu_p3& A, const uint32_t Rw[8], const uint32_t Aw[8], const uint32_t Sw[8],
                                      int policy, TabP& tp) {
-  int ok = sc_is_canonical(Sw);
+  int ok = sc_v1_ok(Sw, policy);
   if (policy == POLICY_LIBSODIUM_1_0_18) {
     ok &= !enc_small_order(Rw);
     ok &= enc_y_canonical(Aw) & !enc_small_order(Aw);

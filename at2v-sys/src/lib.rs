@@ -35,6 +35,12 @@ pub const AT2V_ABI_VERSION: c_int = 9;
 
 pub const AT2V_POLICY_DALEK_V1: c_int = 0;
 pub const AT2V_POLICY_LIBSODIUM_1_0_18: c_int = 1;
+/// dalek built with `legacy_compatibility`: V1 is "the three top bits of S clear", s is used unreduced
+pub const AT2V_POLICY_DALEK_V1_LEGACY: c_int = 2;
+/// include/at2v.h AT2V_MASK_*: bit p of an at2v_policy_mask byte is set iff policy p accepts the record
+pub const AT2V_MASK_DALEK_V1: u8 = 1;
+pub const AT2V_MASK_LIBSODIUM: u8 = 2;
+pub const AT2V_MASK_DALEK_V1_LEGACY: u8 = 4;
 
 pub const AT2V_OK: c_int = 0;
 pub const AT2V_E_INVALID: c_int = -1;
@@ -317,6 +323,10 @@ extern "C" {
                                       d_verdicts: *const u32, d_reasons: *mut u8, hip_stream: *mut c_void) -> c_int;
     pub fn at2v_reject_reasons(ctx: *mut At2vCtx, pk: *const u8, sig: *const u8, n: usize, verdicts: *const u32,
                                reasons: *mut u8) -> c_int;
+    pub fn at2v_policy_mask_device(ctx: *mut At2vCtx, d_pk: *const u8, d_sig: *const u8, n: usize,
+                                   d_verdicts: *const u32, d_mask: *mut u8, hip_stream: *mut c_void) -> c_int;
+    pub fn at2v_policy_mask(ctx: *mut At2vCtx, pk: *const u8, sig: *const u8, n: usize, verdicts: *const u32,
+                            mask: *mut u8) -> c_int;
     pub fn at2v_verify_one_reason(pk: *const u8, sig: *const u8, msg: *const u8, len: usize, policy: c_int) -> c_int;
     pub fn at2v_reason_name(reason: c_int) -> *const c_char;
     pub fn at2v_gen_records_device(ctx: *mut At2vCtx, cfg_seed: u64, first: u64, n: usize, msg_len: u32,
@@ -543,6 +553,23 @@ impl BatchVerifier {
         let mut bytes = vec![AT2V_REASON_UNKNOWN; n];
         check(unsafe { at2v_reject_reasons(self.0, pk.as_ptr(), sig.as_ptr(), n, words.as_ptr(), bytes.as_mut_ptr()) })?;
         Ok(bytes.into_iter().map(RejectReason::from_byte).collect())
+    }
+
+    /// Which policies accept each record of a batch verified by this context, which must have been created with
+    /// AT2V_POLICY_DALEK_V1_LEGACY (any other is refused): `pk` / `sig` as given to `verify`, `verdicts` as it returned
+    /// them. One byte per record, an OR of AT2V_MASK_*: 0, 4, 5 or 7. The pass does not re-verify.
+    pub fn policy_mask(&mut self, pk: &[u8], sig: &[u8], verdicts: &[bool]) -> Result<Vec<u8>, Error> {
+        let n = verdicts.len();
+        if pk.len() != 32 * n || sig.len() != 64 * n {
+            return Err(Error(AT2V_E_INVALID));
+        }
+        let mut words = vec![0u32; (n + 31) / 32];
+        for (i, &v) in verdicts.iter().enumerate() {
+            words[i / 32] |= (v as u32) << (i % 32);
+        }
+        let mut bytes = vec![0u8; n];
+        check(unsafe { at2v_policy_mask(self.0, pk.as_ptr(), sig.as_ptr(), n, words.as_ptr(), bytes.as_mut_ptr()) })?;
+        Ok(bytes)
     }
 
     /// Known senders (at2v_sender_preload): cache the listed 32-byte keys on every device now, so the next launch serves

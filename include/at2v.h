@@ -29,7 +29,8 @@ extern "C" {
  * version 9 added the pinned host memory calls (at2v_host_alloc / _free / _register / _unregister) and appended
  * at2v_info.host_direct_bytes / host_staged_bytes; the known-senders calls (at2v_sender_preload / _unpin / _query,
  * at2v_queue_sender_preload) were added within version 9: they touch no struct, so the number did not move, and a
- * binding that needs them checks that the library exports them; so were the transfers calls (at2v_verify_transfers /
+ * binding that needs them checks that the library exports them; so were AT2V_POLICY_DALEK_V1_LEGACY and the policy mask
+ * (at2v_policy_mask / _device) and the transfers calls (at2v_verify_transfers /
  * _submit / _device, at2v_transfers_workspace_bytes, at2v_queue_submit_transfers);
  * version 8 added the reject reasons (at2v_reject_reasons / _device, at2v_verify_one_reason, at2v_reason_name,
  * at2v_queue_poll_reasons with the AT2V_QUEUE_REASONS queue flag; no struct changed);
@@ -51,7 +52,14 @@ typedef struct at2v_ctx at2v_ctx; /* opaque: device(s), streams, scratch, stagin
 
 typedef enum {
   AT2V_POLICY_DALEK_V1 = 0,         /* ed25519-dalek 1.x PublicKey::verify (the reference; default) */
-  AT2V_POLICY_LIBSODIUM_1_0_18 = 1  /* + libsodium 1.0.18 pre-rejects: A non-canonical / small order, R small order */
+  AT2V_POLICY_LIBSODIUM_1_0_18 = 1, /* + libsodium 1.0.18 pre-rejects: A non-canonical / small order, R small order */
+  AT2V_POLICY_DALEK_V1_LEGACY = 2   /* DALEK_V1 as built with dalek's `legacy_compatibility` feature: the scalar check V1
+                                       is "reject iff S[31] & 0xE0" (s < 2^253) instead of s < l, and [s]B is evaluated
+                                       with the unreduced s, so (A, R || S + l, M) verifies whenever (A, R || S, M) does
+                                       and s + l < 2^253. Everything else is DALEK_V1. Choose it only if the `drop` a
+                                       network runs enables that feature. The acceptance sets are
+                                       nested: LIBSODIUM within DALEK_V1 within DALEK_V1_LEGACY (at2v_policy_mask). Any
+                                       other value is AT2V_E_INVALID wherever a policy is taken. */
 } at2v_policy;
 
 typedef struct {
@@ -317,13 +325,13 @@ const char* at2v_strerror(int code);
  * equation. A record whose verdict bit is set is VALID; any other record gets the LOWEST-numbered failing check, tested
  * in the order of the enum: the key first (as the reference decodes it at ingest), then the signature's scalar (as
  * Signature::from_bytes does), then the policy pre-rejects, then R, then the equation. Under AT2V_POLICY_DALEK_V1
- * reasons 3 and 4 never occur. The reason is a function of (A, R, S, policy) and the verdict bit alone; the message is
+ * and AT2V_POLICY_DALEK_V1_LEGACY reasons 3 and 4 never occur. The reason is a function of (A, R, S, policy) and the verdict bit alone; the message is
  * not needed: if every cheap check passes and the bit is 0, the cause is the equation, by elimination. The pass does
  * NOT re-verify: a caller who hands in a 0 bit for a record that is in fact valid gets AT2V_REASON_EQUATION. */
 typedef enum {
   AT2V_REASON_VALID = 0,      /* verdict bit 1 */
   AT2V_REASON_A_DECODE = 1,   /* V2: A is not a curve point (dalek decompress fails): rpc.rs:269 InvalidArgument */
-  AT2V_REASON_S_RANGE = 2,    /* V1: s >= l */
+  AT2V_REASON_S_RANGE = 2,    /* V1: s >= l; under AT2V_POLICY_DALEK_V1_LEGACY: S[31] & 0xE0, i.e. s >= 2^253 */
   AT2V_REASON_A_POLICY = 3,   /* LIBSODIUM policy only: A's y non-canonical, or A on the small-order blocklist */
   AT2V_REASON_R_POLICY = 4,   /* LIBSODIUM policy only: R on the small-order blocklist */
   AT2V_REASON_R_ENCODING = 5, /* R is not the canonical encoding of a curve point (y >= p, x = 0 with the sign bit, or
@@ -350,6 +358,35 @@ int at2v_reject_reasons(at2v_ctx* ctx, const uint8_t* pk, const uint8_t* sig, si
  * or a negative error code. */
 int at2v_verify_one_reason(const uint8_t pk[32], const uint8_t sig[64], const uint8_t* msg, size_t len, int policy);
 const char* at2v_reason_name(int reason);
+
+/* ---- which policies accept a record (a second, cheap pass in the style of the reject reasons; added within ABI
+ * version 9: no struct changed) ----
+ * A node in a mixed network cares less about "valid or not" than about "would a peer under another rule decide
+ * differently". The three acceptance sets are nested (LIBSODIUM within DALEK_V1 within DALEK_V1_LEGACY), so one verify
+ * under the most permissive policy plus three checks that need no field arithmetic give all three verdicts: one byte per
+ * record, bit p set iff policy p accepts the record. From the verdict bit of a verify over the same records by a context
+ * of AT2V_POLICY_DALEK_V1_LEGACY:
+ *   bit 0  ->  mask 0
+ *   bit 1  ->  AT2V_MASK_DALEK_V1_LEGACY, | AT2V_MASK_DALEK_V1 if s < l, | AT2V_MASK_LIBSODIUM if s < l and A's y is
+ *              canonical and neither A nor R is on libsodium's small-order blocklist
+ * so the mask is 0, 4, 5 or 7. Like the reasons pass it trusts the verdict words and does not re-verify. On a context of
+ * another policy both calls return AT2V_E_INVALID and write nothing (its verdict words cannot tell the three apart). */
+#define AT2V_MASK_DALEK_V1 1u
+#define AT2V_MASK_LIBSODIUM 2u
+#define AT2V_MASK_DALEK_V1_LEGACY 4u
+/* Device buffers, as at2v_reject_reasons_device argument for argument: first device (AT2V_E_NODEVICE on a CPU context),
+ * asynchronous on `hip_stream`, meant to follow the verify launch on the same stream. d_mask receives n bytes (bytes of
+ * rejected records are written too, as 0; nothing is written at or after d_mask + n). d_pk / d_sig / d_mask 16-byte
+ * aligned, d_verdicts 4-byte aligned (AT2V_E_ALIGN). Uses none of the context's scratch sets and never touches the
+ * sender cache: it adds no ordering between verify launches. */
+int at2v_policy_mask_device(at2v_ctx* ctx, const uint8_t* d_pk, const uint8_t* d_sig, size_t n,
+                            const uint32_t* d_verdicts, uint8_t* d_mask, void* hip_stream);
+/* Host buffers, synchronous, as at2v_reject_reasons: a GPU context uploads the records (first device, its stream), a CPU
+ * context runs the same routine on its thread pool. On any error every one of the n bytes is 0 (fail closed: no policy
+ * accepts); with AT2V_CTX_CPU_FALLBACK a device error falls back to the CPU pool and the call returns AT2V_OK. n may be
+ * 0. */
+int at2v_policy_mask(at2v_ctx* ctx, const uint8_t* pk, const uint8_t* sig, size_t n, const uint32_t* verdicts,
+                     uint8_t* mask);
 
 /* ---- signing side (client, src/client.rs:77-78), used to synthesise inputs on the GPU ---- */
 

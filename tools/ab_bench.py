@@ -79,7 +79,8 @@ def main():
                     probe_read(lib)
     for p in a.libs:
         t = np.array(times[p])
-        print(f"{os.path.basename(p):28s} median {np.median(t):8.3f} ms  min {t.min():8.3f}  -> {n / np.median(t) / 1e3:8.2f} M verifies/s")
+        print(f"{p:28s} median {np.median(t):8.3f} ms  min {t.min():8.3f}  max {t.max():8.3f}  -> "
+              f"{n / np.median(t) / 1e3:8.2f} M verifies/s")
     if a.probe:
         for p, (lib, _) in zip(a.libs, libs):
             if hasattr(lib, "at2v_probe_read"):
