@@ -26,10 +26,12 @@ LIB_PATH = os.path.join(_HERE, "libat2v.so")
 POLICY_DALEK_V1 = 0
 POLICY_LIBSODIUM_1_0_18 = 1
 POLICY_DALEK_V1_LEGACY = 2  # dalek built with `legacy_compatibility`: V1 is "the three top bits of S clear", s unreduced
+POLICY_ZIP215 = 4  # the cofactored rule of ZIP-215: s < l, A and R decoded permissively, [8]([s]B - [k]A - R) = 0 (3: unassigned)
 _POLICIES = {"dalek": POLICY_DALEK_V1, "dalek_v1": POLICY_DALEK_V1, "libsodium": POLICY_LIBSODIUM_1_0_18,
              "libsodium_1_0_18": POLICY_LIBSODIUM_1_0_18, "dalek-legacy": POLICY_DALEK_V1_LEGACY,
              "dalek_v1_legacy": POLICY_DALEK_V1_LEGACY, POLICY_DALEK_V1: POLICY_DALEK_V1,
-             POLICY_LIBSODIUM_1_0_18: POLICY_LIBSODIUM_1_0_18, POLICY_DALEK_V1_LEGACY: POLICY_DALEK_V1_LEGACY}
+             POLICY_LIBSODIUM_1_0_18: POLICY_LIBSODIUM_1_0_18, POLICY_DALEK_V1_LEGACY: POLICY_DALEK_V1_LEGACY,
+             "zip215": POLICY_ZIP215, POLICY_ZIP215: POLICY_ZIP215}
 # include/at2v.h AT2V_MASK_*: bit p of a policy-mask byte is set iff policy p accepts the record
 MASK_DALEK_V1, MASK_LIBSODIUM, MASK_DALEK_V1_LEGACY = 1, 2, 4
 

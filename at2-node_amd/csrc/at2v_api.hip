@@ -46,8 +46,8 @@ int at2v_create(const at2v_opts* opts, at2v_ctx** out) {
   if (opts) o = *opts;
   if (o.num_gpus < 0 || o.num_gpus > 64) return AT2V_E_INVALID;
   if (o.policy != AT2V_POLICY_DALEK_V1 && o.policy != AT2V_POLICY_LIBSODIUM_1_0_18 &&
-      o.policy != AT2V_POLICY_DALEK_V1_LEGACY)
-    return AT2V_E_INVALID;
+      o.policy != AT2V_POLICY_DALEK_V1_LEGACY && o.policy != AT2V_POLICY_ZIP215)
+    return AT2V_E_INVALID;  // (3 is unassigned)
   if (o.flags & ~(AT2V_CTX_CPU_FALLBACK | AT2V_CTX_ADMIT_FIRST | AT2V_CTX_BCOMB_WIDE)) return AT2V_E_INVALID;
   if (o.num_gpus == 0) {  // the CPU batch backend: no HIP call at all
     at2v_ctx* c = new (std::nothrow) at2v_ctx;

@@ -134,6 +134,15 @@ AT2V_HD AT2V_INLINE int comb_prechecks(const uint32_t Rw[8], const uint32_t Aw[8
   return ok;
 }
 
+// POLICY_ZIP215 on the comb routes: R_bytes decodes (A's rules, no canonicity terms) and [8](R' - R) is the identity, for
+// R' = [k](-A) + [s]B as the comb sums leave it (a p3 point). One decode of R, one mixed addition and three doublings
+// take the place of the encoding of R' and its inversion.
+AT2V_HD AT2V_INLINE int comb_cofactored_ok(const gu_p3& Rp, const uint32_t Rw[8]) {
+  gu_p3 R;
+  const int ok = gu_frombytes(R, Rw);
+  return ok & gu_cofactored_eq(Rp, R);
+}
+
 // V3 and the recoding of k: kd = signed radix-2^w digits of SHA-512(R || A || M) mod l, e_i + 2^(w-1) in 16-bit fields
 template <class MsgWord>
 AT2V_HD AT2V_INLINE void comb_k_digits(uint32_t kd[kCombDigitWords], const uint32_t Rw[8], const uint32_t Aw[8],
@@ -237,6 +246,7 @@ AT2V_HD AT2V_INLINE int verify_comb_fu(const uint32_t Rw[8], const uint32_t Aw[8
   comb_sum<true>(acc, kd, 0, kCombPos, tc);
   comb_sum<false>(acc, sd, 0, BCombGeom<TabBC::kBits>::kPos, tb);
   AT2V_PHASE(4);
+  if (policy == POLICY_ZIP215) return ok & comb_cofactored_ok(acc, Rw);
   // V5/V6: dalek compares the compressed R' with the 32 bytes of R
   gu_p2 Rp;
   gu_p3_to_p2(Rp, acc);
@@ -246,14 +256,17 @@ AT2V_HD AT2V_INLINE int verify_comb_fu(const uint32_t Rw[8], const uint32_t Aw[8
 // The low-latency split (verify_comb_lat_kernel: one wave per part, on different SIMDs): R decoded on its own instead
 // of R' encoded (no inversion after the sums), R' = Pa0 + Pa1 + Pb from the partial sums, compared projectively.
 // enc(R') == R_bytes <=> R_bytes is canonical (y < p, not x = 0 with the sign bit set), decodes, and dec(R_bytes) = R'
-// (DESIGN.md §4b step 5), so the verdict is dalek's.
-AT2V_HD AT2V_INLINE int comb_decode_r(gu_p3& R, const uint32_t Rw[8]) {
+// (DESIGN.md §4b step 5), so the verdict is dalek's. POLICY_ZIP215: R only has to decode, and [8](R' - R) is tested.
+AT2V_HD AT2V_INLINE int comb_decode_r(gu_p3& R, const uint32_t Rw[8], int policy = POLICY_DALEK_V1) {
   int ok = gu_frombytes(R, Rw);
-  ok &= enc_y_canonical(Rw);
-  ok &= !(fu_iszero(R.X) & (int)(Rw[7] >> 31));
+  if (policy != POLICY_ZIP215) {
+    ok &= enc_y_canonical(Rw);
+    ok &= !(fu_iszero(R.X) & (int)(Rw[7] >> 31));
+  }
   return ok;
 }
-AT2V_HD AT2V_INLINE int comb_check_split(const gu_p3& R, const gu_p3& Pa0, const gu_p3& Pa1, const gu_p3& Pb) {
+AT2V_HD AT2V_INLINE int comb_check_split(const gu_p3& R, const gu_p3& Pa0, const gu_p3& Pa1, const gu_p3& Pb,
+                                         int policy = POLICY_DALEK_V1) {
   gu_cached c;
   gu_p1p1 t;
   gu_p3 S;
@@ -262,6 +275,10 @@ AT2V_HD AT2V_INLINE int comb_check_split(const gu_p3& R, const gu_p3& Pa0, const
   gu_p1p1_to_p3(S, t);
   gu_p3_to_cached(c, Pb);
   gu_add(t, S, c);
+  if (policy == POLICY_ZIP215) {
+    gu_p1p1_to_p3(S, t);
+    return gu_cofactored_eq(S, R);
+  }
   gu_p2 P;
   gu_p1p1_to_p2(P, t);
   // R = (x, y, 1, xy): X = x Z and Y = y Z

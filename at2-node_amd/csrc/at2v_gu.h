@@ -98,6 +98,25 @@ AT2V_HD AT2V_INLINE void gu_p3_to_p2(gu_p2& r, const gu_p3& p) {
   r.Z = p.Z;
 }
 
+// P == (0, 1): X = 0 and Y = Z (X, Y, Z carried)
+AT2V_HD AT2V_INLINE int gu_p2_is_identity(const gu_p2& P) {
+  fu d;
+  fu_sub(d, P.Y, P.Z, FU_KC);
+  return fu_iszero(P.X) & fu_iszero(d);
+}
+
+// [8]P == (0, 1), the cofactored identity test (POLICY_ZIP215): three doublings as the ladders run them, on the output
+// of gu_p1p1_to_p2 (carried, gu_p2_dbl's class). One rolled copy of the doubling.
+AT2V_HD AT2V_INLINE int gu_p2_mul8_is_identity(gu_p2 P) {
+  gu_p1p1 t;
+#pragma unroll 1
+  for (int r = 0; r < 3; ++r) {
+    gu_p2_dbl(t, P);
+    gu_p1p1_to_p2(P, t);
+  }
+  return gu_p2_is_identity(P);
+}
+
 // p3 + cached (add-2008-hwcd-3): A = (Y1-X1)(Y2-X2), B = (Y1+X1)(Y2+X2), C = T1*2dT2, D = Z1*2Z2,
 // x3 = (B-A)/(D+C), y3 = (B+A)/(D-C)
 AT2V_HD AT2V_INLINE void gu_add(gu_p1p1& r, const gu_p3& p, const gu_cached& q) {
@@ -167,6 +186,24 @@ AT2V_HD AT2V_INLINE void gu_niels_cneg(gu_niels& r, int neg) {
     r.ymx.v[i] = neg ? a : b;
     r.xy2d.v[i] = neg ? FU_KC.v[i] - t : t;
   }
+}
+
+// [8](P - R) == (0, 1) for a decoded point R (Z = 1) and P the output of gu_p1p1_to_p3 (or the identity): P - R is a mixed
+// addition with the negated affine Niels form of R (y+x and y-x carried, 2dxy a carried product), the operand classes
+// of the joint table's "2A - R" (tools/gen_fu.py check_group_law, "cofactored tail").
+AT2V_HD AT2V_INLINE int gu_cofactored_eq(const gu_p3& P, const gu_p3& R) {
+  gu_niels n;
+  fu_add(n.ypx, R.Y, R.X);
+  fu_carry(n.ypx);
+  fu_sub(n.ymx, R.Y, R.X, FU_KC);
+  fu_carry(n.ymx);
+  fu_mul_n(n.xy2d, R.T, FU_D2);
+  gu_niels_cneg(n, 1);
+  gu_p1p1 t;
+  gu_madd(t, P, n);
+  gu_p2 D;
+  gu_p1p1_to_p2(D, t);
+  return gu_p2_mul8_is_identity(D);
 }
 
 // dalek CompressedEdwardsY::decompress of two encodings at once: y = LE255(s) mod p, no

@@ -38,7 +38,7 @@ constexpr int kSplitPb = 80 * 64;     // -[t]B, cached form (40 words)
 // sender costs this instead of waiting for its comb (round 3: 0.82-0.94 ms of device time, profiles/r03zg).
 // Verdict words are written by wave 0's lane 0 for every chunk.
 constexpr int kLatBlock = 256;
-__global__ __launch_bounds__(kLatBlock, 1) void verify_comb_lat_kernel(
+__device__ AT2V_INLINE void verify_comb_lat_chunks(
     const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msg,
     uint32_t msg_total, const uint32_t* __restrict__ off, uint32_t n, int policy, uint32_t* __restrict__ verdicts,
     int4* __restrict__ scratch, const int4* __restrict__ btab, CacheArgs c) {
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(kLatBlock, 1) void verify_comb_lat_kernel(
     const DevTabA tp{slot, st0, lane, btab + (size_t)kNumBtabs * kBtabEntries * 8};
     if (all_hit) {
       if (w == 0) {
-        ok0 = comb_decode_r(R, Rw) & comb_prechecks(Rw, Aw, Sw, policy, a_ok);
+        ok0 = comb_decode_r(R, Rw, policy) & comb_prechecks(Rw, Aw, Sw, policy, a_ok);
       } else {
         gu_p3 P;
         gu_p3_identity(P);
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(kLatBlock, 1) void verify_comb_lat_kernel(
     } else if (w == 0) {  // split check, phase 1: V1, the policy pre-checks, A decoded (dalek rules) and [j]A
       ok0 = split_a_side(R, Rw, Aw, Sw, policy, tp);
     } else if (w == 1) {  // R canonical and decoded, [j]R (c1's sign is applied per digit in phase 2)
-      sok[lane] = (uint32_t)split_r_side(Rw, tp);
+      sok[lane] = (uint32_t)split_r_side(Rw, tp, policy);
     } else if (w == 2) {  // k = SHA-512(R || A || M) mod l, the lattice (c0, c1), t = c1 s mod l: digits to LDS
       uint32_t c0d[8], c1d[8];
       int c1_neg, nw_lane;
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(kLatBlock, 1) void verify_comb_lat_kernel(
           p0[q] = part[40 * 64 + q * 64 + lane];
           p1[q] = part[80 * 64 + q * 64 + lane];
         }
-        good = ok0 & (int)sok[lane] & comb_check_split(R, Pa0, Pa1, Pb) & (i < n);
+        good = ok0 & (int)sok[lane] & comb_check_split(R, Pa0, Pa1, Pb, policy) & (i < n);
       } else {  // V = [c0]A + [c1]R - [t]B == identity
         gu_cached c1r, cnb;
         uint32_t* w1 = reinterpret_cast<uint32_t*>(&c1r);
@@ -187,7 +187,8 @@ __global__ __launch_bounds__(kLatBlock, 1) void verify_comb_lat_kernel(
           w1[q] = part[kSplitP1 + q * 64 + lane];
           w2[q] = part[kSplitPb + q * 64 + lane];
         }
-        good = ok0 & (int)sok[lane] & (int)(part[kSplitFlags + lane] & 1) & split_combine(R, c1r, cnb) & (i < n);
+        good = ok0 & (int)sok[lane] & (int)(part[kSplitFlags + lane] & 1) &
+               split_combine(R, c1r, cnb, policy) & (i < n);
       }
       const uint64_t mask = __ballot(good);
       if (lane == 0) {
@@ -197,6 +198,20 @@ __global__ __launch_bounds__(kLatBlock, 1) void verify_comb_lat_kernel(
     }
     __syncthreads();  // the LDS parts are reused by the block's next chunk
   }
+}
+
+// (two kernels over one body, as every verify kernel: at2v_kernels.hip)
+__global__ __launch_bounds__(kLatBlock, 1) void verify_comb_lat_kernel(
+    const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msg,
+    uint32_t msg_total, const uint32_t* __restrict__ off, uint32_t n, int policy, uint32_t* __restrict__ verdicts,
+    int4* __restrict__ scratch, const int4* __restrict__ btab, CacheArgs c) {
+  verify_comb_lat_chunks(pk, sig, msg, msg_total, off, n, cofactorless(policy), verdicts, scratch, btab, c);
+}
+__global__ __launch_bounds__(kLatBlock, 1) void verify_comb_lat_kernel_zip215(
+    const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msg,
+    uint32_t msg_total, const uint32_t* __restrict__ off, uint32_t n, int policy, uint32_t* __restrict__ verdicts,
+    int4* __restrict__ scratch, const int4* __restrict__ btab, CacheArgs c) {
+  verify_comb_lat_chunks(pk, sig, msg, msg_total, off, n, POLICY_ZIP215, verdicts, scratch, btab, c);
 }
 
 // The message reader of one record (verify_chunks' MsgSplit: the fast form when the wave's messages all end 8 bytes
@@ -223,7 +238,8 @@ __device__ AT2V_INLINE int with_msg_reader(const uint8_t* __restrict__ msg, uint
   return body(msgword);
 }
 
-// R' of record i (clamped to the batch) from its key's comb; returns the checks that need no point arithmetic
+// R' of record i (clamped to the batch) from its key's comb; returns the checks that need no point arithmetic, and
+// under POLICY_ZIP215 the whole verdict (comb_cofactored_ok: the callers then skip the encoding and its inversion)
 template <class TabBC>
 __device__ AT2V_INLINE int comb2_point(gu_p3& P, uint32_t i, uint32_t n, const uint8_t* __restrict__ pk,
                                        const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msg,
@@ -278,6 +294,7 @@ __device__ AT2V_INLINE int comb2_point(gu_p3& P, uint32_t i, uint32_t n, const u
     pr->v[kCpLds] += tc.lds_waited;
   }
 #endif
+  if (policy == POLICY_ZIP215) ok &= comb_cofactored_ok(P, Rw);
   return ok;
 }
 
@@ -344,10 +361,12 @@ __device__ AT2V_INLINE int comb2_point_staged(gu_p3& P, uint32_t ii, uint32_t o0
     pr->v[kCpAWait] += tc.waited;
     pr->v[kCpStage] += tc.stage_waited;
     pr->v[kCpLds] += tc.lds_waited;
+    if (policy == POLICY_ZIP215) ok &= comb_cofactored_ok(P, Rw);
     return ok;
   }
 #endif
   comb_point(P, Rw, Aw, Sw, len, staged, tc, tbc);
+  if (policy == POLICY_ZIP215) ok &= comb_cofactored_ok(P, Rw);
   return ok;
 }
 
@@ -358,7 +377,7 @@ __device__ AT2V_INLINE int comb2_point_staged(gu_p3& P, uint32_t ii, uint32_t o0
 // through the half-size ladder.
 // kPart: the chunks are 256 entries of the classify kernel's hit list (every record cached), verdict bits set by atomic
 // OR; no ladder branch.
-template <bool kPart = false>
+template <bool kPart = false, bool kZip = false>
 __device__ AT2V_INLINE void verify_chunks_comb4(
     int4* astage, int4* rstage, const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig,
     const uint8_t* __restrict__ msg, uint32_t msg_total, const uint32_t* __restrict__ off, uint32_t n, int policy,
@@ -389,6 +408,10 @@ __device__ AT2V_INLINE void verify_chunks_comb4(
   const uint32_t c_first = wib < (int)kHalf ? blockIdx.x * kHalf + wib
                                             : gridDim.x * kHalf + blockIdx.x * kHalf + (wib - kHalf);
   auto clamp = [n](uint32_t i) { return i < n ? i : n - 1; };
+  // kZip: the ZIP215 twin (at2v_kernels.hip). `policy` is captured by reference below (the ladder branch's message
+  // reader), so it lives in memory and a value passed in could not be seen through: the policy the two branches use is
+  // formed where it is used, from the template argument or with cofactorless() (at2v_kern_tables.h)
+  const int pol = kZip ? POLICY_ZIP215 : cofactorless(policy);
 #ifdef AT2V_COMB_PROBE
   CombProbe probe;
   CombProbe* const pr = kPart ? &probe : nullptr;
@@ -446,7 +469,7 @@ __device__ AT2V_INLINE void verify_chunks_comb4(
         const int aq = q == 0 ? a_ok[0] : q == 1 ? a_ok[1] : q == 2 ? a_ok[2] : a_ok[3];
         const int cq = q == 0 ? cidx[0] : q == 1 ? cidx[1] : q == 2 ? cidx[2] : cidx[3];
         gu_p3 P;
-        const int okq = comb2_point(P, rq, n, pk, sig, msg, msg_total, off, policy, aq,
+        const int okq = comb2_point(P, rq, n, pk, sig, msg, msg_total, off, pol, aq,
                                     comb + (size_t)cq * (kCombBytes / 16), tbc, sa, sr, lane AT2V_CP_ARG);
         okm |= okq << q;
         slot_store(slot + 8 * q, reinterpret_cast<const int32_t*>(&P), 30);  // X, Y, Z (T not needed)
@@ -454,33 +477,37 @@ __device__ AT2V_INLINE void verify_chunks_comb4(
 #ifdef AT2V_COMB_PROBE
       const unsigned long long t_fin0 = __builtin_amdgcn_s_memtime();
 #endif
-      // Montgomery's trick: 1/Z_q = Z_{q^1} / (Z_q Z_{q^1}), and 1/(Z0 Z1), 1/(Z2 Z3) from one inversion
-      fu inv01, inv23;
-      {
-        fu z0, z1, z2, z3, zz01, zz23, zz, inv;
-        slot_load(reinterpret_cast<int32_t*>(z0.v), slot + 5, 10);
-        slot_load(reinterpret_cast<int32_t*>(z1.v), slot + 8 + 5, 10);
-        slot_load(reinterpret_cast<int32_t*>(z2.v), slot + 16 + 5, 10);
-        slot_load(reinterpret_cast<int32_t*>(z3.v), slot + 24 + 5, 10);
-        fu_mulc(zz01, z0, z1);
-        fu_mulc(zz23, z2, z3);
-        fu_mulc(zz, zz01, zz23);
-        fu_invert(inv, zz);
-        fu_mulc(inv01, inv, zz23);
-        fu_mulc(inv23, inv, zz01);
-      }
-      int goodm = 0;
+      // POLICY_ZIP215 (wave-uniform): comb2_point's verdicts are final, nothing is encoded and nothing inverted
+      int goodm = okm;
+      if (pol != POLICY_ZIP215) {
+        // Montgomery's trick: 1/Z_q = Z_{q^1} / (Z_q Z_{q^1}), and 1/(Z0 Z1), 1/(Z2 Z3) from one inversion
+        fu inv01, inv23;
+        {
+          fu z0, z1, z2, z3, zz01, zz23, zz, inv;
+          slot_load(reinterpret_cast<int32_t*>(z0.v), slot + 5, 10);
+          slot_load(reinterpret_cast<int32_t*>(z1.v), slot + 8 + 5, 10);
+          slot_load(reinterpret_cast<int32_t*>(z2.v), slot + 16 + 5, 10);
+          slot_load(reinterpret_cast<int32_t*>(z3.v), slot + 24 + 5, 10);
+          fu_mulc(zz01, z0, z1);
+          fu_mulc(zz23, z2, z3);
+          fu_mulc(zz, zz01, zz23);
+          fu_invert(inv, zz);
+          fu_mulc(inv01, inv, zz23);
+          fu_mulc(inv23, inv, zz01);
+        }
+        goodm = 0;
 #pragma unroll 1
-      for (int q = 0; q < 4; ++q) {
-        const uint32_t rq = q == 0 ? rec[0] : q == 1 ? rec[1] : q == 2 ? rec[2] : rec[3];
-        fu zp, zi;
-        gu_p2 Q;
-        slot_load(reinterpret_cast<int32_t*>(zp.v), slot + 8 * (q ^ 1) + 5, 10);  // the partner's Z
-        slot_load(reinterpret_cast<int32_t*>(&Q), slot + 8 * q, 30);
-        uint32_t Rw[8];
-        load8(Rw, sig + (size_t)rq * 64);
-        fu_mulc(zi, q < 2 ? inv01 : inv23, zp);
-        goodm |= (((okm >> q) & 1) & gu_encode_eq_zi(Q, zi, Rw)) << q;
+        for (int q = 0; q < 4; ++q) {
+          const uint32_t rq = q == 0 ? rec[0] : q == 1 ? rec[1] : q == 2 ? rec[2] : rec[3];
+          fu zp, zi;
+          gu_p2 Q;
+          slot_load(reinterpret_cast<int32_t*>(zp.v), slot + 8 * (q ^ 1) + 5, 10);  // the partner's Z
+          slot_load(reinterpret_cast<int32_t*>(&Q), slot + 8 * q, 30);
+          uint32_t Rw[8];
+          load8(Rw, sig + (size_t)rq * 64);
+          fu_mulc(zi, q < 2 ? inv01 : inv23, zp);
+          goodm |= (((okm >> q) & 1) & gu_encode_eq_zi(Q, zi, Rw)) << q;
+        }
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) good[q] = (goodm >> q) & 1;
@@ -499,7 +526,8 @@ __device__ AT2V_INLINE void verify_chunks_comb4(
         load8(Aw, pk + (size_t)ii * 32);
         const uint32_t o0 = off[ii], len = off[ii + 1] - o0;
         const int gq = with_msg_reader(msg, msg_total, o0, len, [&](auto& mwd) {
-          return verify_half_fu(Rw, Aw, Sw, len, mwd, policy, ta, tr, tb0, tb1, wmax);
+          return verify_half_fu(Rw, Aw, Sw, len, mwd, kZip ? POLICY_ZIP215 : cofactorless(policy), ta, tr, tb0, tb1,
+                                wmax);
         });
         good[0] = q == 0 ? gq : good[0];  // (selects, not a runtime index into a register array)
         good[1] = q == 1 ? gq : good[1];
@@ -556,8 +584,17 @@ __global__ __launch_bounds__(kBlock, kVerifyWavesPerSimd) void verify_kernel_com
     int4* __restrict__ scratch, const int4* __restrict__ btab, uint32_t* __restrict__ chunk_queue, CacheArgs c) {
   __shared__ int4 astage[kWavesPerBlock * 10 * 64];
   __shared__ int4 rstage[kWavesPerBlock * 10 * 64];
-  verify_chunks_comb4<false>(astage, rstage, pk, sig, msg, msg_total, off, n, policy, verdicts, scratch, btab,
-                             chunk_queue, c);
+  verify_chunks_comb4<false, false>(astage, rstage, pk, sig, msg, msg_total, off, n, policy, verdicts, scratch, btab,
+                                    chunk_queue, c);
+}
+__global__ __launch_bounds__(kBlock, kVerifyWavesPerSimd) void verify_kernel_comb_zip215(
+    const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msg,
+    uint32_t msg_total, const uint32_t* __restrict__ off, uint32_t n, int policy, uint32_t* __restrict__ verdicts,
+    int4* __restrict__ scratch, const int4* __restrict__ btab, uint32_t* __restrict__ chunk_queue, CacheArgs c) {
+  __shared__ int4 astage[kWavesPerBlock * 10 * 64];
+  __shared__ int4 rstage[kWavesPerBlock * 10 * 64];
+  verify_chunks_comb4<false, true>(astage, rstage, pk, sig, msg, msg_total, off, n, policy, verdicts, scratch, btab,
+                                   chunk_queue, c);
 }
 
 // The classify kernel's hit list by comb additions, kRecs records per lane (chunks of 64 kRecs list positions): each
@@ -647,68 +684,76 @@ __device__ AT2V_INLINE void verify_comb_hits(int4* astage, int4* rstage, const u
 #ifdef AT2V_COMB_PROBE
     const unsigned long long t_fin0 = __builtin_amdgcn_s_memtime();
 #endif
-    {
-      fu z0, z1, zp0, zp1, inv;
-      zload(z0, 0);
-      zload(z1, 1);
-#ifdef AT2V_COMB_PROBE
-      AT2V_CPROBE(probe.v[kCpSlot], asm volatile("s_waitcnt vmcnt(0)" ::: "memory"));
-#endif
-      fu_mulc(zp0, z0, z1);
-      zload(z0, 2);
-      zload(z1, 3);
-#ifdef AT2V_COMB_PROBE
-      AT2V_CPROBE(probe.v[kCpSlot], asm volatile("s_waitcnt vmcnt(0)" ::: "memory"));
-#endif
-      fu_mulc(zp1, z0, z1);
-      if constexpr (kRecs == 4) {
-        fu_mulc(z0, zp0, zp1);
-        fu_invert(inv, z0);
-        fu_mulc(z0, inv, zp1);  // 1 / (Z0 Z1)
-        slot_store(pinv, reinterpret_cast<const int32_t*>(z0.v), 10);
-        fu_mulc(z0, inv, zp0);  // 1 / (Z2 Z3)
-        slot_store(pinv + 3, reinterpret_cast<const int32_t*>(z0.v), 10);
-      } else {
-        fu zp2, zp3, zq0, zq1;
-        zload(z0, 4);
-        zload(z1, 5);
-        fu_mulc(zp2, z0, z1);
-        zload(z0, 6);
-        zload(z1, 7);
-        fu_mulc(zp3, z0, z1);
-        fu_mulc(zq0, zp0, zp1);
-        fu_mulc(zq1, zp2, zp3);
-        fu_mulc(z0, zq0, zq1);
-        fu_invert(inv, z0);
-        fu_mulc(z0, inv, zq1);  // 1 / (Z0 Z1 Z2 Z3)
-        fu_mulc(z1, z0, zp1);   // 1 / (Z0 Z1)
-        slot_store(pinv, reinterpret_cast<const int32_t*>(z1.v), 10);
-        fu_mulc(z1, z0, zp0);   // 1 / (Z2 Z3)
-        slot_store(pinv + 3, reinterpret_cast<const int32_t*>(z1.v), 10);
-        fu_mulc(z0, inv, zq0);  // 1 / (Z4 Z5 Z6 Z7)
-        fu_mulc(z1, z0, zp3);   // 1 / (Z4 Z5)
-        slot_store(pinv + 6, reinterpret_cast<const int32_t*>(z1.v), 10);
-        fu_mulc(z1, z0, zp2);   // 1 / (Z6 Z7)
-        slot_store(pinv + 9, reinterpret_cast<const int32_t*>(z1.v), 10);
-      }
-    }
+    if (policy == POLICY_ZIP215) {  // (wave-uniform) comb2_point's verdicts are final: nothing encoded or inverted
 #pragma unroll 1
-    for (int q = 0; q < kRecs; ++q) {
-      const uint32_t pos = i0 + 64 * q, pc = pos < nh ? pos : nh - 1;
-      const uint32_t rq = pp.hidx[pc];
-      fu zp, ip, zi;
-      gu_p2 Q;
-      zload(zp, q ^ 1);  // the partner's Z
-      slot_load(reinterpret_cast<int32_t*>(ip.v), pinv + 3 * (q >> 1), 10);
-      slot_load(reinterpret_cast<int32_t*>(&Q), slot + 8 * q, 30);
-      uint32_t Rw[8];
-      load8(Rw, sig + (size_t)rq * 64);
+      for (int q = 0; q < kRecs; ++q) {
+        const uint32_t pos = i0 + 64 * q, pc = pos < nh ? pos : nh - 1;
+        verdict_or(verdicts, pp.hidx[pc], (okm >> q) & 1, pos < nh, lane);
+      }
+    } else {
+      {
+        fu z0, z1, zp0, zp1, inv;
+        zload(z0, 0);
+        zload(z1, 1);
 #ifdef AT2V_COMB_PROBE
-      AT2V_CPROBE(probe.v[kCpSlot], asm volatile("s_waitcnt vmcnt(0)" ::: "memory"));
+        AT2V_CPROBE(probe.v[kCpSlot], asm volatile("s_waitcnt vmcnt(0)" ::: "memory"));
 #endif
-      fu_mulc(zi, ip, zp);
-      const int good = ((okm >> q) & 1) & gu_encode_eq_zi(Q, zi, Rw);
-      verdict_or(verdicts, rq, good, pos < nh, lane);
+        fu_mulc(zp0, z0, z1);
+        zload(z0, 2);
+        zload(z1, 3);
+#ifdef AT2V_COMB_PROBE
+        AT2V_CPROBE(probe.v[kCpSlot], asm volatile("s_waitcnt vmcnt(0)" ::: "memory"));
+#endif
+        fu_mulc(zp1, z0, z1);
+        if constexpr (kRecs == 4) {
+          fu_mulc(z0, zp0, zp1);
+          fu_invert(inv, z0);
+          fu_mulc(z0, inv, zp1);  // 1 / (Z0 Z1)
+          slot_store(pinv, reinterpret_cast<const int32_t*>(z0.v), 10);
+          fu_mulc(z0, inv, zp0);  // 1 / (Z2 Z3)
+          slot_store(pinv + 3, reinterpret_cast<const int32_t*>(z0.v), 10);
+        } else {
+          fu zp2, zp3, zq0, zq1;
+          zload(z0, 4);
+          zload(z1, 5);
+          fu_mulc(zp2, z0, z1);
+          zload(z0, 6);
+          zload(z1, 7);
+          fu_mulc(zp3, z0, z1);
+          fu_mulc(zq0, zp0, zp1);
+          fu_mulc(zq1, zp2, zp3);
+          fu_mulc(z0, zq0, zq1);
+          fu_invert(inv, z0);
+          fu_mulc(z0, inv, zq1);  // 1 / (Z0 Z1 Z2 Z3)
+          fu_mulc(z1, z0, zp1);   // 1 / (Z0 Z1)
+          slot_store(pinv, reinterpret_cast<const int32_t*>(z1.v), 10);
+          fu_mulc(z1, z0, zp0);   // 1 / (Z2 Z3)
+          slot_store(pinv + 3, reinterpret_cast<const int32_t*>(z1.v), 10);
+          fu_mulc(z0, inv, zq0);  // 1 / (Z4 Z5 Z6 Z7)
+          fu_mulc(z1, z0, zp3);   // 1 / (Z4 Z5)
+          slot_store(pinv + 6, reinterpret_cast<const int32_t*>(z1.v), 10);
+          fu_mulc(z1, z0, zp2);   // 1 / (Z6 Z7)
+          slot_store(pinv + 9, reinterpret_cast<const int32_t*>(z1.v), 10);
+        }
+      }
+#pragma unroll 1
+      for (int q = 0; q < kRecs; ++q) {
+        const uint32_t pos = i0 + 64 * q, pc = pos < nh ? pos : nh - 1;
+        const uint32_t rq = pp.hidx[pc];
+        fu zp, ip, zi;
+        gu_p2 Q;
+        zload(zp, q ^ 1);  // the partner's Z
+        slot_load(reinterpret_cast<int32_t*>(ip.v), pinv + 3 * (q >> 1), 10);
+        slot_load(reinterpret_cast<int32_t*>(&Q), slot + 8 * q, 30);
+        uint32_t Rw[8];
+        load8(Rw, sig + (size_t)rq * 64);
+#ifdef AT2V_COMB_PROBE
+        AT2V_CPROBE(probe.v[kCpSlot], asm volatile("s_waitcnt vmcnt(0)" ::: "memory"));
+#endif
+        fu_mulc(zi, ip, zp);
+        const int good = ((okm >> q) & 1) & gu_encode_eq_zi(Q, zi, Rw);
+        verdict_or(verdicts, rq, good, pos < nh, lane);
+      }
     }
 #ifdef AT2V_COMB_PROBE
     const unsigned long long t_book0 = __builtin_amdgcn_s_memtime();
@@ -739,6 +784,19 @@ __device__ AT2V_INLINE void verify_comb_hits(int4* astage, int4* rstage, const u
 // partitioned cached launches: the classify kernel's hit list by comb additions, four records per lane (eight per lane,
 // one inversion for eight, measured 1.4% slower on 1M records from 64 senders: one 512-record chunk per wave leaves
 // the chunk queue nothing to balance, profiles/r05n/abcomb.txt), [s]B from the context's 20-bit or 24-bit comb of B
+__device__ AT2V_INLINE void verify_comb_part_chunks(
+    int4* astage, int4* rstage, const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig,
+    const uint8_t* __restrict__ msg, uint32_t msg_total, const uint32_t* __restrict__ off, uint32_t n, int policy,
+    uint32_t* __restrict__ verdicts, int4* __restrict__ scratch, uint32_t* __restrict__ chunk_queue, const CacheArgs& c,
+    const PartArgs& p) {
+  const uint32_t nh = __builtin_amdgcn_readfirstlane(p.counts[0]);
+  if (c.bcomb_bits == kBCombBits)  // AT2V_CTX_BCOMB_WIDE
+    verify_comb_hits<4, kBCombBits>(astage, rstage, pk, sig, msg, msg_total, off, n, policy, verdicts, scratch,
+                                    chunk_queue, c, p, nh);
+  else
+    verify_comb_hits<4, kBCombMidBits>(astage, rstage, pk, sig, msg, msg_total, off, n, policy, verdicts, scratch,
+                                       chunk_queue, c, p, nh);
+}
 __global__ __launch_bounds__(kBlock, kVerifyWavesPerSimd) void verify_kernel_comb_part(
     const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msg,
     uint32_t msg_total, const uint32_t* __restrict__ off, uint32_t n, int policy, uint32_t* __restrict__ verdicts,
@@ -747,13 +805,19 @@ __global__ __launch_bounds__(kBlock, kVerifyWavesPerSimd) void verify_kernel_com
   __shared__ int4 astage[kWavesPerBlock * 10 * 64];
   __shared__ int4 rstage[kWavesPerBlock * 10 * 64];
   (void)btab;
-  const uint32_t nh = __builtin_amdgcn_readfirstlane(p.counts[0]);
-  if (c.bcomb_bits == kBCombBits)  // AT2V_CTX_BCOMB_WIDE
-    verify_comb_hits<4, kBCombBits>(astage, rstage, pk, sig, msg, msg_total, off, n, policy, verdicts, scratch,
-                                    chunk_queue, c, p, nh);
-  else
-    verify_comb_hits<4, kBCombMidBits>(astage, rstage, pk, sig, msg, msg_total, off, n, policy, verdicts, scratch,
-                                       chunk_queue, c, p, nh);
+  verify_comb_part_chunks(astage, rstage, pk, sig, msg, msg_total, off, n, cofactorless(policy), verdicts, scratch,
+                          chunk_queue, c, p);
+}
+__global__ __launch_bounds__(kBlock, kVerifyWavesPerSimd) void verify_kernel_comb_part_zip215(
+    const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msg,
+    uint32_t msg_total, const uint32_t* __restrict__ off, uint32_t n, int policy, uint32_t* __restrict__ verdicts,
+    int4* __restrict__ scratch, const int4* __restrict__ btab, uint32_t* __restrict__ chunk_queue, CacheArgs c,
+    PartArgs p) {
+  __shared__ int4 astage[kWavesPerBlock * 10 * 64];
+  __shared__ int4 rstage[kWavesPerBlock * 10 * 64];
+  (void)btab;
+  verify_comb_part_chunks(astage, rstage, pk, sig, msg, msg_total, off, n, POLICY_ZIP215, verdicts, scratch,
+                          chunk_queue, c, p);
 }
 
 }  // namespace at2v

@@ -13,6 +13,13 @@
 
 namespace at2v {
 
+// What a verify kernel of the cofactorless policies (0..2) hands its body as the policy: the same value, in a form the
+// compiler can see is never POLICY_ZIP215, so every cofactored branch of the shared headers folds away in that kernel
+// (at2v_kernels.hip; the ZIP215 twins pass the constant).
+static_assert(POLICY_ZIP215 == 4 && (POLICY_DALEK_V1 | POLICY_LIBSODIUM_1_0_18 | POLICY_DALEK_V1_LEGACY) < 4,
+              "the cofactorless policies fit two bits; ZIP215 does not");
+__device__ AT2V_INLINE int cofactorless(int policy) { return policy & 3; }
+
 constexpr int kBlock = 512;  // verify threads per block: 8 waves, both waves of every SIMD in one workgroup
 constexpr int kWavesPerBlock = kBlock / 64;
 constexpr int kVerifyWavesPerSimd = 2;  // register budget: 512 / waves VGPR+AGPR per lane

@@ -65,6 +65,10 @@ struct Pace {
 // cache_lookup_kernel + cache_build_kernel, launched just before on the same stream).
 // The body is a device function under two kernels with their own parameter lists, so the uncached kernel keeps exactly
 // round 2's signature and code (an extra-parameter template of it measured ~1% slower: profiles/r03b, r03d).
+// Every verify kernel exists twice: under its own name for the cofactorless policies, which hands the
+// body cofactorless(policy), a value the compiler can see is not POLICY_ZIP215, so the cofactored branches of the shared
+// headers fold away and the kernel keeps the registers, scratch and code it had before that policy existed; and as
+// <name>_zip215, which hands it the constant and is launched by ZIP215 contexts only (AT2V_LAUNCH_VERIFY).
 // kPart (partitioned cached launches, at2v_cache.h PartArgs): chunks are 64 entries of the classify kernel's lists
 // instead of 64 consecutive records: with kCache ([j]A tables) the hit list's chunks (every record cached: A's decode and
 // table skipped) and then the miss list's, without it the miss list alone (the comb kernel takes the hits). A record's
@@ -215,8 +219,18 @@ __global__ __launch_bounds__(kBlock, kVerifyWavesPerSimd) void verify_kernel(
     uint32_t* __restrict__ chunk_queue) {
   __shared__ int4 astage[kWavesPerBlock * 10 * 64];
   __shared__ int4 rstage[kWavesPerBlock * 10 * 64];
-  verify_chunks<false>(astage, rstage, pk, sig, msg, msg_total, off, n, policy, verdicts, scratch, btab, chunk_queue,
-                       nullptr);
+  verify_chunks<false>(astage, rstage, pk, sig, msg, msg_total, off, n, cofactorless(policy), verdicts, scratch, btab,
+                       chunk_queue, nullptr);
+}
+__global__ __launch_bounds__(kBlock, kVerifyWavesPerSimd) void verify_kernel_zip215(
+    const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msg,
+    uint32_t msg_total, const uint32_t* __restrict__ off, uint32_t n, int policy, uint32_t* __restrict__ verdicts,
+    int4* __restrict__ scratch, const int4* __restrict__ btab,
+    uint32_t* __restrict__ chunk_queue) {
+  __shared__ int4 astage[kWavesPerBlock * 10 * 64];
+  __shared__ int4 rstage[kWavesPerBlock * 10 * 64];
+  verify_chunks<false>(astage, rstage, pk, sig, msg, msg_total, off, n, POLICY_ZIP215, verdicts, scratch, btab,
+                       chunk_queue, nullptr);
 }
 
 // the same with the per-sender A cache (at2v_opts.sender_cache, tables [j]A)
@@ -227,8 +241,18 @@ __global__ __launch_bounds__(kBlock, kVerifyWavesPerSimd) void verify_kernel_cac
     uint32_t* __restrict__ chunk_queue, CacheArgs c) {
   __shared__ int4 astage[kWavesPerBlock * 10 * 64];
   __shared__ int4 rstage[kWavesPerBlock * 10 * 64];
-  verify_chunks<true>(astage, rstage, pk, sig, msg, msg_total, off, n, policy, verdicts, scratch, btab, chunk_queue,
-                      &c);
+  verify_chunks<true>(astage, rstage, pk, sig, msg, msg_total, off, n, cofactorless(policy), verdicts, scratch, btab,
+                      chunk_queue, &c);
+}
+__global__ __launch_bounds__(kBlock, kVerifyWavesPerSimd) void verify_kernel_cached_zip215(
+    const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msg,
+    uint32_t msg_total, const uint32_t* __restrict__ off, uint32_t n, int policy, uint32_t* __restrict__ verdicts,
+    int4* __restrict__ scratch, const int4* __restrict__ btab,
+    uint32_t* __restrict__ chunk_queue, CacheArgs c) {
+  __shared__ int4 astage[kWavesPerBlock * 10 * 64];
+  __shared__ int4 rstage[kWavesPerBlock * 10 * 64];
+  verify_chunks<true>(astage, rstage, pk, sig, msg, msg_total, off, n, POLICY_ZIP215, verdicts, scratch, btab,
+                      chunk_queue, &c);
 }
 
 // Partitioned cached launches (at2v_cache.h PartArgs): the ladder over the classify kernel's miss list (sender_comb: the
@@ -240,8 +264,18 @@ __global__ __launch_bounds__(kBlock, kVerifyWavesPerSimd) void verify_kernel_mis
     uint32_t* __restrict__ chunk_queue, PartArgs p) {
   __shared__ int4 astage[kWavesPerBlock * 10 * 64];
   __shared__ int4 rstage[kWavesPerBlock * 10 * 64];
-  verify_chunks<false, true>(astage, rstage, pk, sig, msg, msg_total, off, n, policy, verdicts, scratch, btab,
-                             chunk_queue, nullptr, &p);
+  verify_chunks<false, true>(astage, rstage, pk, sig, msg, msg_total, off, n, cofactorless(policy), verdicts, scratch,
+                             btab, chunk_queue, nullptr, &p);
+}
+__global__ __launch_bounds__(kBlock, kVerifyWavesPerSimd) void verify_kernel_miss_zip215(
+    const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msg,
+    uint32_t msg_total, const uint32_t* __restrict__ off, uint32_t n, int policy, uint32_t* __restrict__ verdicts,
+    int4* __restrict__ scratch, const int4* __restrict__ btab,
+    uint32_t* __restrict__ chunk_queue, PartArgs p) {
+  __shared__ int4 astage[kWavesPerBlock * 10 * 64];
+  __shared__ int4 rstage[kWavesPerBlock * 10 * 64];
+  verify_chunks<false, true>(astage, rstage, pk, sig, msg, msg_total, off, n, POLICY_ZIP215, verdicts, scratch,
+                             btab, chunk_queue, nullptr, &p);
 }
 __global__ __launch_bounds__(kBlock, kVerifyWavesPerSimd) void verify_kernel_tables_part(
     const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msg,
@@ -250,8 +284,18 @@ __global__ __launch_bounds__(kBlock, kVerifyWavesPerSimd) void verify_kernel_tab
     uint32_t* __restrict__ chunk_queue, CacheArgs c, PartArgs p) {
   __shared__ int4 astage[kWavesPerBlock * 10 * 64];
   __shared__ int4 rstage[kWavesPerBlock * 10 * 64];
-  verify_chunks<true, true>(astage, rstage, pk, sig, msg, msg_total, off, n, policy, verdicts, scratch, btab,
-                            chunk_queue, &c, &p);
+  verify_chunks<true, true>(astage, rstage, pk, sig, msg, msg_total, off, n, cofactorless(policy), verdicts, scratch,
+                            btab, chunk_queue, &c, &p);
+}
+__global__ __launch_bounds__(kBlock, kVerifyWavesPerSimd) void verify_kernel_tables_part_zip215(
+    const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msg,
+    uint32_t msg_total, const uint32_t* __restrict__ off, uint32_t n, int policy, uint32_t* __restrict__ verdicts,
+    int4* __restrict__ scratch, const int4* __restrict__ btab,
+    uint32_t* __restrict__ chunk_queue, CacheArgs c, PartArgs p) {
+  __shared__ int4 astage[kWavesPerBlock * 10 * 64];
+  __shared__ int4 rstage[kWavesPerBlock * 10 * 64];
+  verify_chunks<true, true>(astage, rstage, pk, sig, msg, msg_total, off, n, POLICY_ZIP215, verdicts, scratch,
+                            btab, chunk_queue, &c, &p);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -261,12 +305,10 @@ __global__ __launch_bounds__(kBlock, kVerifyWavesPerSimd) void verify_kernel_tab
 // lanes evaluate V = P0 + P1 (verify_pair_combine). Chunks c = 32-record groups, grid-strided.
 constexpr int kPairBlock = 256;
 constexpr int kPairWaves = kPairBlock / 64;
-__global__ __launch_bounds__(kPairBlock, 1) void verify_pair_kernel(
-    const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msg,
-    uint32_t msg_total, const uint32_t* __restrict__ off, uint32_t n, int policy, uint32_t* __restrict__ verdicts,
-    int4* __restrict__ scratch, const int4* __restrict__ btab) {
-  __shared__ int4 pstage[kPairWaves * 10 * 64];
-  __shared__ int4 bstage[kPairWaves * 10 * 64];
+__device__ AT2V_INLINE void verify_pair_chunks(
+    int4* pstage, int4* bstage, const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig,
+    const uint8_t* __restrict__ msg, uint32_t msg_total, const uint32_t* __restrict__ off, uint32_t n, int policy,
+    uint32_t* __restrict__ verdicts, int4* __restrict__ scratch, const int4* __restrict__ btab) {
   const int lane = threadIdx.x & 63;
   const int wib = AT2V_UNIFORM(threadIdx.x >> 6);  // wave-uniform: the LDS stage addresses live in SGPRs
   const int side = lane & 1;
@@ -308,7 +350,7 @@ __global__ __launch_bounds__(kPairBlock, 1) void verify_pair_kernel(
 #pragma unroll
     for (int q = 0; q < 40; ++q) pw[q] = (uint32_t)__shfl_xor((int)cw[q], 1);
     ok &= __shfl_xor(ok, 1);
-    const int good = ok & verify_pair_combine(Pm, cp) & (i < n);
+    const int good = ok & verify_pair_combine(Pm, cp, policy) & (i < n);
     const uint64_t mask = __ballot(good);
     if (lane == 0) {  // record r's verdict is lane 2r's bit: compress the even bits of the ballot
       uint64_t x = mask & 0x5555555555555555ull;
@@ -320,6 +362,23 @@ __global__ __launch_bounds__(kPairBlock, 1) void verify_pair_kernel(
       verdicts[c] = (uint32_t)x;
     }
   }
+}
+
+__global__ __launch_bounds__(kPairBlock, 1) void verify_pair_kernel(
+    const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msg,
+    uint32_t msg_total, const uint32_t* __restrict__ off, uint32_t n, int policy, uint32_t* __restrict__ verdicts,
+    int4* __restrict__ scratch, const int4* __restrict__ btab) {
+  __shared__ int4 pstage[kPairWaves * 10 * 64];
+  __shared__ int4 bstage[kPairWaves * 10 * 64];
+  verify_pair_chunks(pstage, bstage, pk, sig, msg, msg_total, off, n, cofactorless(policy), verdicts, scratch, btab);
+}
+__global__ __launch_bounds__(kPairBlock, 1) void verify_pair_kernel_zip215(
+    const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msg,
+    uint32_t msg_total, const uint32_t* __restrict__ off, uint32_t n, int policy, uint32_t* __restrict__ verdicts,
+    int4* __restrict__ scratch, const int4* __restrict__ btab) {
+  __shared__ int4 pstage[kPairWaves * 10 * 64];
+  __shared__ int4 bstage[kPairWaves * 10 * 64];
+  verify_pair_chunks(pstage, bstage, pk, sig, msg, msg_total, off, n, POLICY_ZIP215, verdicts, scratch, btab);
 }
 
 size_t cache_entry_bytes() { return (size_t)kCacheEntryGranules * 16; }
@@ -433,6 +492,13 @@ hipError_t launch_build_btab(int4* out, hipStream_t stream) {
 
 size_t part_bytes_per_record() { return 12; }  // hidx, hinfo, midx
 
+// a ZIP215 context launches the kernel's cofactored twin (`policy` is launch_verify's)
+#define AT2V_LAUNCH_VERIFY(kernel, ...)                                             \
+  do {                                                                              \
+    if (policy == POLICY_ZIP215) hipLaunchKernelGGL(kernel##_zip215, __VA_ARGS__); \
+    else hipLaunchKernelGGL(kernel, __VA_ARGS__);                                  \
+  } while (0)
+
 hipError_t launch_verify(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, uint32_t msg_total,
                          const uint32_t* off, uint32_t n, int policy, uint32_t* verdicts, int4* scratch,
                          const int4* btab, int grid, uint32_t pair_max, hipStream_t stream,
@@ -444,7 +510,7 @@ hipError_t launch_verify(const uint8_t* pk, const uint8_t* sig, const uint8_t* m
     const uint32_t cap_blocks = (uint32_t)grid * kWavesPerBlock / kPairWaves;
     uint32_t g = (nchunks + kPairWaves - 1) / kPairWaves;
     g = g < cap_blocks ? g : cap_blocks;
-    hipLaunchKernelGGL(verify_pair_kernel, dim3(g), dim3(kPairBlock), 0, stream, pk, sig, msg, msg_total, off, n,
+    AT2V_LAUNCH_VERIFY(verify_pair_kernel, dim3(g), dim3(kPairBlock), 0, stream, pk, sig, msg, msg_total, off, n,
                        policy, verdicts, scratch, btab);
     return hipGetLastError();
   }
@@ -479,12 +545,12 @@ hipError_t launch_verify(const uint8_t* pk, const uint8_t* sig, const uint8_t* m
     if (cache->comb) {
       const uint32_t need2 = ((n + 255) / 256 + kWavesPerBlock / 2 - 1) / (kWavesPerBlock / 2);
       const int g2 = (int)((uint32_t)grid < need2 ? (uint32_t)grid : need2);
-      hipLaunchKernelGGL(verify_kernel_comb_part, dim3(g2), dim3(kBlock), 0, stream, pk, sig, msg, msg_total, off, n,
+      AT2V_LAUNCH_VERIFY(verify_kernel_comb_part, dim3(g2), dim3(kBlock), 0, stream, pk, sig, msg, msg_total, off, n,
                          policy, verdicts, scratch, btab, queue + 1, *cache, pa);
-      hipLaunchKernelGGL(verify_kernel_miss, dim3(g), dim3(kBlock), 0, stream, pk, sig, msg, msg_total, off, n, policy,
+      AT2V_LAUNCH_VERIFY(verify_kernel_miss, dim3(g), dim3(kBlock), 0, stream, pk, sig, msg, msg_total, off, n, policy,
                          verdicts, scratch, btab, queue, pa);
     } else {
-      hipLaunchKernelGGL(verify_kernel_tables_part, dim3(g), dim3(kBlock), 0, stream, pk, sig, msg, msg_total, off, n,
+      AT2V_LAUNCH_VERIFY(verify_kernel_tables_part, dim3(g), dim3(kBlock), 0, stream, pk, sig, msg, msg_total, off, n,
                          policy, verdicts, scratch, btab, queue, *cache, pa);
     }
     return hipGetLastError();
@@ -492,7 +558,7 @@ hipError_t launch_verify(const uint8_t* pk, const uint8_t* sig, const uint8_t* m
   if (cache) {  // the kernels look their senders up themselves (at2v_cache.h); builds follow on the build stream
     if (cache->comb && n <= pair_max) {  // small batches: the four-wave split, one block per 64 records
       const uint32_t gl = nchunks < (uint32_t)grid ? nchunks : (uint32_t)grid;
-      hipLaunchKernelGGL(verify_comb_lat_kernel, dim3(gl), dim3(kLatBlock), 0, stream, pk, sig, msg, msg_total, off, n,
+      AT2V_LAUNCH_VERIFY(verify_comb_lat_kernel, dim3(gl), dim3(kLatBlock), 0, stream, pk, sig, msg, msg_total, off, n,
                          policy, verdicts, scratch, btab, *cache);
       return hipGetLastError();
     }
@@ -500,15 +566,15 @@ hipError_t launch_verify(const uint8_t* pk, const uint8_t* sig, const uint8_t* m
       const uint32_t crec = 256u;  // records per chunk (verify_chunks_comb4)
       const uint32_t need2 = ((n + crec - 1) / crec + kWavesPerBlock / 2 - 1) / (kWavesPerBlock / 2);
       const int g2 = (int)((uint32_t)grid < need2 ? (uint32_t)grid : need2);
-      hipLaunchKernelGGL(verify_kernel_comb, dim3(g2), dim3(kBlock), 0, stream, pk, sig, msg, msg_total, off, n, policy,
+      AT2V_LAUNCH_VERIFY(verify_kernel_comb, dim3(g2), dim3(kBlock), 0, stream, pk, sig, msg, msg_total, off, n, policy,
                          verdicts, scratch, btab, queue, *cache);
       return hipGetLastError();
     }
-    hipLaunchKernelGGL(verify_kernel_cached, dim3(g), dim3(kBlock), 0, stream, pk, sig, msg, msg_total, off, n, policy,
+    AT2V_LAUNCH_VERIFY(verify_kernel_cached, dim3(g), dim3(kBlock), 0, stream, pk, sig, msg, msg_total, off, n, policy,
                        verdicts, scratch, btab, queue, *cache);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL(verify_kernel, dim3(g), dim3(kBlock), 0, stream, pk, sig, msg, msg_total, off, n, policy,
+  AT2V_LAUNCH_VERIFY(verify_kernel, dim3(g), dim3(kBlock), 0, stream, pk, sig, msg, msg_total, off, n, policy,
                      verdicts, scratch, btab, queue);
   return hipGetLastError();
 }

@@ -27,12 +27,14 @@ enum {
 // rules), V1 (s < l; LEGACY policy: s < 2^253), (LIBSODIUM policy) A canonical and not blocklisted, R not blocklisted,
 // then R is the canonical encoding of a curve point (the conditions verify_half_fu puts on R_bytes); if all of them
 // hold, the equation failed, by elimination. It does not re-verify: a valid record handed in with a 0 bit gets
-// REASON_EQUATION. The cheap checks are evaluated for every lane before the decodes, and R is decoded only by lanes
+// REASON_EQUATION. Under POLICY_ZIP215 R is decoded by A's rules, so REASON_R_ENCODING means "R is not on the curve" only
+// (a non-canonical y, or x = 0 with the sign bit, is no cause), and the equation is the cofactored one. The cheap checks
+// are evaluated for every lane before the decodes, and R is decoded only by lanes
 // still undecided, so a wave pays at most two square-root chains.
 AT2V_HD AT2V_INLINE int reject_reason(const uint32_t Aw[8], const uint32_t Rw[8], const uint32_t Sw[8], int policy) {
-  const int sodium = policy == POLICY_LIBSODIUM_1_0_18;
+  const int sodium = policy == POLICY_LIBSODIUM_1_0_18, zip = policy == POLICY_ZIP215;
   int cheap = 0;  // the first failing check after A's decode that needs no field arithmetic (0: none)
-  if (!enc_y_canonical(Rw)) cheap = REASON_R_ENCODING;
+  if (!zip && !enc_y_canonical(Rw)) cheap = REASON_R_ENCODING;
   if (sodium && enc_small_order(Rw)) cheap = REASON_R_POLICY;
   if (sodium && (!enc_y_canonical(Aw) || enc_small_order(Aw))) cheap = REASON_A_POLICY;
   if (!sc_v1_ok(Sw, policy)) cheap = REASON_S_RANGE;
@@ -45,7 +47,7 @@ AT2V_HD AT2V_INLINE int reject_reason(const uint32_t Aw[8], const uint32_t Rw[8]
     gu_p3 P;
     const int ok = gu_frombytes(P, W);
     if (q == 0) r = ok ? cheap : REASON_A_DECODE;
-    else r = (ok & !(fu_iszero(P.X) & (int)(Rw[7] >> 31))) ? REASON_EQUATION : REASON_R_ENCODING;
+    else r = (ok & (zip | !(fu_iszero(P.X) & (int)(Rw[7] >> 31)))) ? REASON_EQUATION : REASON_R_ENCODING;
   }
   return r;
 }

@@ -23,7 +23,9 @@ AT2V_HD AT2V_INLINE int sc_is_canonical(const uint32_t s[8]) {
 }
 
 // Verdict semantics (include/at2v.h at2v_policy).
-enum { POLICY_DALEK_V1 = 0, POLICY_LIBSODIUM_1_0_18 = 1, POLICY_DALEK_V1_LEGACY = 2 };
+// (3 is unassigned and refused wherever a policy is taken.) POLICY_ZIP215 is the cofactored rule: V1 as DALEK_V1, no
+// canonicity check on R, accept iff [8]([s]B - [k]A - R) is the identity.
+enum { POLICY_DALEK_V1 = 0, POLICY_LIBSODIUM_1_0_18 = 1, POLICY_DALEK_V1_LEGACY = 2, POLICY_ZIP215 = 4 };
 
 // V1 under `policy` (uniform over a launch): s < l, or under dalek's legacy_compatibility rule only the three top bits
 // of S clear (s < 2^253), s then being used unreduced. Everything downstream takes any s < 2^253: sc_mul_signed reduces

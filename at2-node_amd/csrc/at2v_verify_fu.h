@@ -62,6 +62,13 @@ namespace at2v {
 #define AT2V_TAB_MADD 1
 #endif
 
+// The conditions on R_bytes beside "it decodes" (x: the decoded R's X): canonical, i.e. y < p and not x = 0 with the sign
+// bit set. POLICY_ZIP215 decodes R by A's rules and has neither (wave-uniform: the policy is a kernel argument).
+AT2V_HD AT2V_INLINE int r_canonical_ok(const uint32_t Rw[8], const fu& x, int policy) {
+  if (policy == POLICY_ZIP215) return 1;
+  return enc_y_canonical(Rw) & !(fu_iszero(x) & (int)(Rw[7] >> 31));
+}
+
 // [j]P, j = 0..8, cached form, into tp (one table; the A/B form of the interleaved build). P1 is a decoded point (Z = 1).
 template <class TabP>
 AT2V_HD AT2V_INLINE void build_a_table_from(const gu_p3& P1, TabP& tp) {
@@ -122,7 +129,7 @@ AT2V_HD AT2V_INLINE int verify_half_fu(const uint32_t Rw[8], const uint32_t Aw[8
       for (int i = 0; i < 8; ++i) W[i] = q ? Rw[i] : Aw[i];
       gu_p3 P;
       okd &= gu_frombytes(P, W);
-      if (q) okd &= enc_y_canonical(Rw) & !(fu_iszero(P.X) & (int)(Rw[7] >> 31));
+      if (q) okd &= r_canonical_ok(Rw, P.X, policy);
       TabP& tp = q ? tr : ta;
       tp.park(P);
     }
@@ -141,8 +148,7 @@ AT2V_HD AT2V_INLINE int verify_half_fu(const uint32_t Rw[8], const uint32_t Aw[8
     if (AT2V_TABLES_EARLY != 3) build_a_table_from(A, ta);
   }
   ok &= gu_frombytes(R, Rw);
-  ok &= enc_y_canonical(Rw);
-  ok &= !(fu_iszero(R.X) & (int)(Rw[7] >> 31));
+  ok &= r_canonical_ok(Rw, R.X, policy);
   if (AT2V_TABLES_EARLY != 2) build_a_table_from(R, tr);
 #else
   if (kCacheable && a_cached) {
@@ -157,8 +163,7 @@ AT2V_HD AT2V_INLINE int verify_half_fu(const uint32_t Rw[8], const uint32_t Aw[8
     ok &= gu_frombytes(R, Rw);
 #endif
   }
-  ok &= enc_y_canonical(Rw);
-  ok &= !(fu_iszero(R.X) & (int)(Rw[7] >> 31));
+  ok &= r_canonical_ok(Rw, R.X, policy);
 #endif
 #if AT2V_PARK_POINTS && !AT2V_TABLES_EARLY && !AT2V_DECODE_LATE && !AT2V_DECODE_LOOP
   // A and R are not used again until the tables are built (after SHA-512, the lattice reduction and the recoding), and
@@ -237,8 +242,7 @@ AT2V_HD AT2V_INLINE int verify_half_fu(const uint32_t Rw[8], const uint32_t Aw[8
   {
     gu_p3 R;
     ok &= gu_frombytes(R, Rw);
-    ok &= enc_y_canonical(Rw);
-    ok &= !(fu_iszero(R.X) & (int)(Rw[7] >> 31));
+    ok &= r_canonical_ok(Rw, R.X, policy);
     if (hs.c1_neg) {
       fu_neg(R.X, R.X, FU_KC);
       fu_carry(R.X);
@@ -403,6 +407,9 @@ AT2V_HD AT2V_INLINE int verify_half_fu(const uint32_t Rw[8], const uint32_t Aw[8
     gu_p1p1_to_p2(R2, tt);
   }
   AT2V_PHASE(4);
+  // ZIP215: [8]V == identity. V = [c1](R - R') in the full group (c0 = c1 k mod 8l), [8](R - R') has order 1 or l and
+  // 0 < |c1| < l, so this is [8]R == [8]R' 
+  if (policy == POLICY_ZIP215) return ok & gu_p2_mul8_is_identity(R2);
   // V == identity: X = 0 and Y = Z
   fu d;
   fu_sub(d, R2.Y, R2.Z, FU_KC);
@@ -527,8 +534,7 @@ AT2V_HD AT2V_INLINE int verify_half_fu_joint(const uint32_t Rw[8], const uint32_
   gu_p3 A, R;
   ok &= gu_frombytes(A, Aw);
   ok &= gu_frombytes(R, Rw);
-  ok &= enc_y_canonical(Rw);
-  ok &= !(fu_iszero(R.X) & (int)(Rw[7] >> 31));
+  ok &= r_canonical_ok(Rw, R.X, policy);
   AT2V_PHASE(1);
   pace.mark(10);
   // V3: k = SHA-512(R || A || M) mod l
@@ -659,6 +665,9 @@ AT2V_HD AT2V_INLINE int verify_half_fu_joint(const uint32_t Rw[8], const uint32_
     neg_cur = neg_next;
   }
   AT2V_PHASE(4);
+  // ZIP215: [8]V == identity. V = [c1](R - R') in the full group (c0 = c1 k mod 8l), [8](R - R') has order 1 or l and
+  // 0 < |c1| < l, so this is [8]R == [8]R' 
+  if (policy == POLICY_ZIP215) return ok & gu_p2_mul8_is_identity(R2);
   // V == identity: X = 0 and Y = Z
   fu d;
   fu_sub(d, R2.Y, R2.Z, FU_KC);
@@ -688,10 +697,10 @@ AT2V_HD AT2V_INLINE int verify_pair_part(int side, const uint32_t Rw[8], const u
       ok &= enc_y_canonical(Aw) & !enc_small_order(Aw);
     }
   } else {
-    ok = enc_y_canonical(Rw);
+    ok = 1;
   }
   ok &= gu_frombytes(P, side ? Rw : Aw);
-  if (side) ok &= !(fu_iszero(P.X) & (int)(Rw[7] >> 31));
+  if (side) ok &= r_canonical_ok(Rw, P.X, policy);
   AT2V_PHASE(1);
   uint32_t k[8];
   {
@@ -776,10 +785,16 @@ AT2V_HD AT2V_INLINE int verify_pair_part(int side, const uint32_t Rw[8], const u
 }
 
 // V = mine + partner (the partner's point in cached form) == identity: in p1p1 (E, H, G, F), x = E/G and y = H/F,
-// so V = (0, 1) <=> E = 0 and H = F
-AT2V_HD AT2V_INLINE int verify_pair_combine(const gu_p3& mine, const gu_cached& partner) {
+// so V = (0, 1) <=> E = 0 and H = F. POLICY_ZIP215: V is completed to a point and [8]V tested.
+AT2V_HD AT2V_INLINE int verify_pair_combine(const gu_p3& mine, const gu_cached& partner,
+                                           int policy = POLICY_DALEK_V1) {
   gu_p1p1 v;
   gu_add(v, mine, partner);
+  if (policy == POLICY_ZIP215) {
+    gu_p2 V;
+    gu_p1p1_to_p2(V, v);
+    return gu_p2_mul8_is_identity(V);
+  }
   fu d;
   fu_sub(d, v.T, v.Y, FU_K2C);  // F + K - H: H = B + A is a sum of two carried elements, F may exceed FU_KC
   return fu_iszero(v.X) & fu_iszero(d);
@@ -849,11 +864,10 @@ AT2V_HD AT2V_INLINE int split_a_side(gu_p3& A, const uint32_t Rw[8], const uint3
 }
 
 template <class TabP>
-AT2V_HD AT2V_INLINE int split_r_side(const uint32_t Rw[8], TabP& tp) {
+AT2V_HD AT2V_INLINE int split_r_side(const uint32_t Rw[8], TabP& tp, int policy = POLICY_DALEK_V1) {
   gu_p3 R;
-  int ok = enc_y_canonical(Rw);
-  ok &= gu_frombytes(R, Rw);
-  ok &= !(fu_iszero(R.X) & (int)(Rw[7] >> 31));
+  int ok = gu_frombytes(R, Rw);
+  ok &= r_canonical_ok(Rw, R.X, policy);
   build_a_table_from(R, tp);
   return ok;
 }
@@ -902,13 +916,14 @@ AT2V_HD AT2V_INLINE void split_neg_tb(gu_cached& out, const uint32_t* td, const 
   gu_cached_cneg(out, 1);
 }
 
-// V = P0 + P1 + (-[t]B) == identity (P1 and -[t]B in cached form)
-AT2V_HD AT2V_INLINE int split_combine(const gu_p3& P0, const gu_cached& P1, const gu_cached& nTB) {
+// V = P0 + P1 + (-[t]B) == identity, or [8]V under POLICY_ZIP215 (P1 and -[t]B in cached form)
+AT2V_HD AT2V_INLINE int split_combine(const gu_p3& P0, const gu_cached& P1, const gu_cached& nTB,
+                                     int policy = POLICY_DALEK_V1) {
   gu_p1p1 t;
   gu_add(t, P0, P1);
   gu_p3 S;
   gu_p1p1_to_p3(S, t);
-  return verify_pair_combine(S, nTB);
+  return verify_pair_combine(S, nTB, policy);
 }
 
 // Per-sender cache entry (at2v_opts.sender_cache; AT2 senders repeat, accounts/account.rs:36-43): dalek's decode verdict

@@ -37,6 +37,9 @@ pub const AT2V_POLICY_DALEK_V1: c_int = 0;
 pub const AT2V_POLICY_LIBSODIUM_1_0_18: c_int = 1;
 /// dalek built with `legacy_compatibility`: V1 is "the three top bits of S clear", s is used unreduced
 pub const AT2V_POLICY_DALEK_V1_LEGACY: c_int = 2;
+/// the cofactored rule of ZIP-215: s < l, A and R decoded by dalek's `decompress` (no canonicity check on R), accept iff
+/// [8]([s]B - [k]A - R) is the identity. Value 3 is unassigned and refused. Not part of the policy mask.
+pub const AT2V_POLICY_ZIP215: c_int = 4;
 /// include/at2v.h AT2V_MASK_*: bit p of an at2v_policy_mask byte is set iff policy p accepts the record
 pub const AT2V_MASK_DALEK_V1: u8 = 1;
 pub const AT2V_MASK_LIBSODIUM: u8 = 2;

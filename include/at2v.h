@@ -30,7 +30,7 @@ extern "C" {
  * at2v_info.host_direct_bytes / host_staged_bytes; the known-senders calls (at2v_sender_preload / _unpin / _query,
  * at2v_queue_sender_preload) were added within version 9: they touch no struct, so the number did not move, and a
  * binding that needs them checks that the library exports them; so were AT2V_POLICY_DALEK_V1_LEGACY and the policy mask
- * (at2v_policy_mask / _device) and the transfers calls (at2v_verify_transfers /
+ * (at2v_policy_mask / _device), AT2V_POLICY_ZIP215 (one enum value) and the transfers calls (at2v_verify_transfers /
  * _submit / _device, at2v_transfers_workspace_bytes, at2v_queue_submit_transfers);
  * version 8 added the reject reasons (at2v_reject_reasons / _device, at2v_verify_one_reason, at2v_reason_name,
  * at2v_queue_poll_reasons with the AT2V_QUEUE_REASONS queue flag; no struct changed);
@@ -53,13 +53,34 @@ typedef struct at2v_ctx at2v_ctx; /* opaque: device(s), streams, scratch, stagin
 typedef enum {
   AT2V_POLICY_DALEK_V1 = 0,         /* ed25519-dalek 1.x PublicKey::verify (the reference; default) */
   AT2V_POLICY_LIBSODIUM_1_0_18 = 1, /* + libsodium 1.0.18 pre-rejects: A non-canonical / small order, R small order */
-  AT2V_POLICY_DALEK_V1_LEGACY = 2   /* DALEK_V1 as built with dalek's `legacy_compatibility` feature: the scalar check V1
+  AT2V_POLICY_DALEK_V1_LEGACY = 2,  /* DALEK_V1 as built with dalek's `legacy_compatibility` feature: the scalar check V1
                                        is "reject iff S[31] & 0xE0" (s < 2^253) instead of s < l, and [s]B is evaluated
                                        with the unreduced s, so (A, R || S + l, M) verifies whenever (A, R || S, M) does
                                        and s + l < 2^253. Everything else is DALEK_V1. Choose it only if the `drop` a
                                        network runs enables that feature. The acceptance sets are
-                                       nested: LIBSODIUM within DALEK_V1 within DALEK_V1_LEGACY (at2v_policy_mask). Any
-                                       other value is AT2V_E_INVALID wherever a policy is taken. */
+                                       nested: LIBSODIUM within DALEK_V1 within DALEK_V1_LEGACY (at2v_policy_mask). */
+  /* 3 is unassigned: AT2V_E_INVALID wherever a policy is taken, like every value not named here. */
+  AT2V_POLICY_ZIP215 = 4            /* the cofactored rule of ZIP-215 (ed25519-zebra, Go's ed25519consensus, dalek's
+                                       verify_batch), the only one under which batch and single verification agree on
+                                       every input:
+                                         1. s < l, as DALEK_V1 (not the legacy rule);
+                                         2. A and R both decode by dalek's CompressedEdwardsY::decompress: y is the low
+                                            255 bits mod p (y >= p accepted), x = 0 with the sign bit set accepted, a y
+                                            that is not on the curve rejected; no canonicity check on R, no small-order
+                                            pre-rejects;
+                                         3. k = SHA-512(R_bytes || A_bytes || M) mod l over the bytes as given;
+                                         4. accept iff [8]([s]B - [k]A - R) is the identity.
+                                       The four rules side by side: DALEK_V1 is 1, 3 and the cofactorless equation
+                                       enc([s]B - [k]A) == R_bytes (so R must be canonical); LIBSODIUM adds its
+                                       pre-rejects; LEGACY relaxes 1 to s < 2^253; ZIP215 keeps 1 and relaxes the rest.
+                                       Nesting: a DALEK_V1 accept implies a ZIP215 accept (s < l, R canonical and equal
+                                       to R'), hence so does a LIBSODIUM accept. DALEK_V1_LEGACY and ZIP215 are NOT
+                                       nested: legacy takes s >= l, which ZIP215 refuses; ZIP215 takes torsion-shifted
+                                       and non-canonical R, which legacy refuses. For that reason a ZIP215 context is
+                                       refused by at2v_policy_mask like any non-legacy context: a cofactored verdict
+                                       cannot tell the cofactorless rules apart without field arithmetic, and there
+                                       is no ZIP215 bit in the mask. Choose it if the network's verifier is one of the
+                                       implementations above. */
 } at2v_policy;
 
 typedef struct {
@@ -325,7 +346,7 @@ const char* at2v_strerror(int code);
  * equation. A record whose verdict bit is set is VALID; any other record gets the LOWEST-numbered failing check, tested
  * in the order of the enum: the key first (as the reference decodes it at ingest), then the signature's scalar (as
  * Signature::from_bytes does), then the policy pre-rejects, then R, then the equation. Under AT2V_POLICY_DALEK_V1
- * and AT2V_POLICY_DALEK_V1_LEGACY reasons 3 and 4 never occur. The reason is a function of (A, R, S, policy) and the verdict bit alone; the message is
+ * and AT2V_POLICY_DALEK_V1_LEGACY and AT2V_POLICY_ZIP215 reasons 3 and 4 never occur. The reason is a function of (A, R, S, policy) and the verdict bit alone; the message is
  * not needed: if every cheap check passes and the bit is 0, the cause is the equation, by elimination. The pass does
  * NOT re-verify: a caller who hands in a 0 bit for a record that is in fact valid gets AT2V_REASON_EQUATION. */
 typedef enum {
@@ -335,8 +356,10 @@ typedef enum {
   AT2V_REASON_A_POLICY = 3,   /* LIBSODIUM policy only: A's y non-canonical, or A on the small-order blocklist */
   AT2V_REASON_R_POLICY = 4,   /* LIBSODIUM policy only: R on the small-order blocklist */
   AT2V_REASON_R_ENCODING = 5, /* R is not the canonical encoding of a curve point (y >= p, x = 0 with the sign bit, or
-                                 not on the curve): no R' can compare equal to these bytes */
-  AT2V_REASON_EQUATION = 6,   /* everything well-formed; enc([s]B - [k]A) != R */
+                                 not on the curve): no R' can compare equal to these bytes. Under AT2V_POLICY_ZIP215:
+                                 R is not on the curve, only */
+  AT2V_REASON_EQUATION = 6,   /* everything well-formed; enc([s]B - [k]A) != R (AT2V_POLICY_ZIP215: [8]([s]B - [k]A - R)
+                                 is not the identity) */
   AT2V_REASON_UNKNOWN = 255   /* 0xff: the call or the batch failed; neither valid nor invalid */
 } at2v_reason;
 

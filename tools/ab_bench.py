@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """A/B kernel-time comparison of libat2v builds, interleaved rounds in ONE process (guide rule 24).
-usage: python3 tools/ab_bench.py lib1.so lib2.so ... [--n 1048576] [--rounds 5]
-Also checks every build returns all-valid verdicts for the generated batch."""
+usage: python3 tools/ab_bench.py lib1.so lib2.so ... [--n 1048576] [--rounds 5] [--policies 0,0,4]
+--policies gives each library's context its AT2V_POLICY_* value (default 0 for all; a library may be named twice), so the
+same records can be timed under two rules of one build. Also checks every build returns all-valid verdicts for the generated batch."""
 import argparse
 import ctypes
 import os
@@ -20,7 +21,7 @@ class Opts(ctypes.Structure):  # include/at2v.h at2v_opts (ABI v6)
                 ("cpu_threads", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
-def open_lib(path, comb=False, wide=False):
+def open_lib(path, comb=False, wide=False, policy=0):
     lib = ctypes.CDLL(os.path.abspath(path), mode=os.RTLD_LOCAL)
     P = ctypes.c_void_p
     lib.at2v_create.argtypes = [P, ctypes.POINTER(P)]
@@ -28,7 +29,7 @@ def open_lib(path, comb=False, wide=False):
     lib.at2v_gen_records_senders_device.argtypes = [P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t,
                                                     ctypes.c_uint32, ctypes.c_uint64, P, P, P, P, P]
     h = P()
-    o = Opts(0, 1, 0, 0, 1024 if comb else 0, 1 if comb else 0, 0, 4 if (comb and wide) else 0)
+    o = Opts(0, 1, policy, 0, 1024 if comb else 0, 1 if comb else 0, 0, 4 if (comb and wide) else 0)
     assert lib.at2v_create(ctypes.byref(o), ctypes.byref(h)) == 0
     return lib, h
 
@@ -45,10 +46,14 @@ def main():
     ap.add_argument("--wide", action="store_true", help="with --comb: the wide comb of B (AT2V_CTX_BCOMB_WIDE)")
     ap.add_argument("--probe", action="store_true",
                     help="builds with -DAT2V_COMB_PROBE: print the comb kernel's per-wait cycle sums (rounds 2..)")
+    ap.add_argument("--policies", default="", help="comma-separated AT2V_POLICY_* value per library (default: all 0)")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     n, L = a.n, a.msg_len
-    libs = [open_lib(p, a.comb, a.wide) for p in a.libs]
+    policies = [int(x) for x in a.policies.split(",")] if a.policies else [0] * len(a.libs)
+    assert len(policies) == len(a.libs), "--policies needs one value per library"
+    libs = [open_lib(p, a.comb, a.wide, pol) for p, pol in zip(a.libs, policies)]
+    names = [f"{p} policy {pol}" for p, pol in zip(a.libs, policies)]
     s = torch.cuda.current_stream()
     d_pk = torch.empty(n * 32, dtype=torch.uint8, device="cuda")
     d_sig = torch.empty(n * 64, dtype=torch.uint8, device="cuda")
@@ -59,9 +64,9 @@ def main():
     assert lib0.at2v_gen_records_senders_device(h0, 0x4154325F, 0, n, L, a.senders, d_pk.data_ptr(), d_sig.data_ptr(),
                                                 d_msg.data_ptr(), d_off.data_ptr(), s.cuda_stream) == 0
     torch.cuda.synchronize()
-    times = {p: [] for p in a.libs}
+    times = {p: [] for p in names}
     for r in range(a.rounds + 1):
-        for p, (lib, h) in zip(a.libs, libs):
+        for p, (lib, h) in zip(names, libs):
             d_ver.zero_()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(s)
@@ -77,9 +82,9 @@ def main():
             for lib, _ in libs:
                 if hasattr(lib, "at2v_probe_read"):
                     probe_read(lib)
-    for p in a.libs:
+    for p in names:
         t = np.array(times[p])
-        print(f"{p:28s} median {np.median(t):8.3f} ms  min {t.min():8.3f}  max {t.max():8.3f}  -> "
+        print(f"{p:36s} median {np.median(t):8.3f} ms  min {t.min():8.3f}  max {t.max():8.3f}  -> "
               f"{n / np.median(t) / 1e3:8.2f} M verifies/s")
     if a.probe:
         for p, (lib, _) in zip(a.libs, libs):

@@ -328,6 +328,29 @@ def check_group_law(C, K):
     for (P, n, nm) in ((A, nR, "joint 2A"), (R, nA, "joint 2R")):
         D = j_p3(j_dbl(P, nm), nm + " ->p3"); j_cached(D, nm)
         j_cached(j_p3(j_madd(D, n, nm + "+-"), nm + "+- ->p3"), nm + "+-")
+    # --- cofactored tail (POLICY_ZIP215: gu_p2_mul8_is_identity, gu_cofactored_eq, verify_pair_combine), the same
+    #     sequence on per-limb maxima. Every site is in a class the ladder already uses; nothing needs a carry before it.
+    def j_p2(p1p1, nm):                      # gu_p1p1_to_p2: three products, each a carried element
+        x, y, z, t = p1p1
+        m.mul(x, t, nm + " X"); m.mul(z, y, nm + " Y'", True); m.mul(z, t, nm + " Z")
+        return (C, C, C)
+
+    def j_mul8(P2, nm):                      # three doublings, each completed to p2; then X = 0, Y - Z = 0
+        for r in range(3):
+            P2 = j_p2(j_dbl(P2, f"{nm} dbl{r}"), f"{nm} dbl{r} ->p2")
+        assert dom(KC, P2[2])                # the identity test subtracts Z with K_C
+
+    P3 = (C, C, C, C)                        # the output of gu_p1p1_to_p3, or the identity
+    # three doublings after the last addition of a ladder (p3 + cached, p3 + Niels, a doubling), completed to p2
+    for (p1p1, nm) in ((addr, "tail add"), (madd, "tail madd"), (dbl, "tail dbl")):
+        j_mul8(j_p2(p1p1, nm + " ->p2"), nm)
+    # the subtraction of a decoded point (comb routes): P - R as a mixed addition with R's negated affine Niels form
+    # (y + x and y - x carried, 2d x y a carried product: the joint table's niels_of), completed, then [8]
+    nRd = j_niels(j_cached(R, "tail R"))
+    j_mul8(j_p2(j_madd(P3, nRd, "tail P-R"), "tail P-R ->p2"), "tail P-R")
+    # the completion after the pair combine (verify_pair_combine: p3 + cached, the partner's point as gu_p3_to_cached
+    # leaves it, not carried), then [8]
+    j_mul8(j_p2(addr, "tail pair ->p2"), "tail pair")
     # --- decode: u = y^2 + (p - 1), v = d y^2 + 1; checks on v x^2 -+ u
     u = add(C, K["PM1"])
     v = add(C, [1] + [0] * 9)
