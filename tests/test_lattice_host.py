@@ -51,6 +51,30 @@ def check(pairs, res, slack):
     return worst
 
 
+def corner_ks():
+    """the corner list (tests/probe_cases.py sends the same list through the probe library)"""
+    rng = random.Random(8)
+    ks = [0, 1, 2, 3, 7, 8, 9, 16, L - 1, L - 2, (L - 1) // 2, 2**126, 2**127, 2**128, 2**200, 2**252 - 1,
+          (1 << 128) + 1, 5, 12345678901234567890, N8 // 7 % L, N8 // 2**40 % L, N8 // 2**100 % L]
+    ks += [rng.randrange(2**64) for _ in range(50)]               # tiny k: one huge first quotient
+    ks += [L - rng.randrange(2**64) for _ in range(50)]
+    ks += [(N8 // rng.randrange(2, 2**60)) % L for _ in range(100)]  # huge quotients deeper in the run
+    return [(k, rng.randrange(L)) for k in ks]
+
+
+def near_threshold_ks():
+    """k whose Euclid remainders straddle the stopping threshold ceil(sqrt(8l)) (the probe tests send the same list)"""
+    import math
+    rng = random.Random(9)
+    thr = math.isqrt(N8) + 1
+    ks = []
+    for _ in range(300):  # k = 8l / (thr + small) lands the first remainder next to the threshold
+        d = thr + rng.randrange(-2**20, 2**20)
+        ks.append((N8 // d) % L)
+        ks.append((N8 // d + rng.randrange(1, 2**16)) % L)
+    return [(k, rng.randrange(L)) for k in ks]
+
+
 def test_random_k(exe):
     rng = random.Random(7)
     pairs = [(rng.randrange(L), rng.randrange(L)) for _ in range(20000)]
@@ -61,13 +85,7 @@ def test_random_k(exe):
 
 
 def test_corner_k(exe):
-    rng = random.Random(8)
-    ks = [0, 1, 2, 3, 7, 8, 9, 16, L - 1, L - 2, (L - 1) // 2, 2**126, 2**127, 2**128, 2**200, 2**252 - 1,
-          (1 << 128) + 1, 5, 12345678901234567890, N8 // 7 % L, N8 // 2**40 % L, N8 // 2**100 % L]
-    ks += [rng.randrange(2**64) for _ in range(50)]               # tiny k: one huge first quotient
-    ks += [L - rng.randrange(2**64) for _ in range(50)]
-    ks += [(N8 // rng.randrange(2, 2**60)) % L for _ in range(100)]  # huge quotients deeper in the run
-    pairs = [(k, rng.randrange(L)) for k in ks]
+    pairs = corner_ks()
     res = run(exe, pairs)
     worst = check(pairs, res, slack=4)
     # the kernel's 64 radix-16 windows need bits <= 255 (verify_half fails a lane closed above that): the
@@ -78,15 +96,7 @@ def test_corner_k(exe):
 def test_bits_bound_near_lehmer_threshold(exe):
     """k whose Euclid remainders straddle the stopping threshold ceil(sqrt(8l)) at every depth the
     Lehmer rounds reach: the chosen vector must stay short (no candidate built from the huge row)"""
-    import math
-    rng = random.Random(9)
-    thr = math.isqrt(N8) + 1
-    ks = []
-    for _ in range(300):  # k = 8l / (thr + small) lands the first remainder next to the threshold
-        d = thr + rng.randrange(-2**20, 2**20)
-        ks.append((N8 // d) % L)
-        ks.append((N8 // d + rng.randrange(1, 2**16)) % L)
-    pairs = [(k, rng.randrange(L)) for k in ks]
+    pairs = near_threshold_ks()
     res = run(exe, pairs)
     worst = check(pairs, res, slack=4)
     assert worst <= 253, worst

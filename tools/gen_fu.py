@@ -217,12 +217,14 @@ class Model:
     def __init__(self, carried):
         self.C = carried
         self.sq_sites = {False: [], True: []}    # [double]: (input maxima, where, narrow) of every fu_sq / fu_sq2 site
+        self.mul_sites = []                      # (f maxima, g maxima, where) of every one-MAD-wrap multiplication site
 
     def mul(self, f, g, where, narrow=False):
         assert all(f[i] <= MUL_F[i] for i in range(10)), (where, "f", f)
         assert all(g[i] <= MUL_G[i] for i in range(10)), (where, "g", g)
         if narrow:
             assert prove(MCOLS, f, g, where)[1] < 2**32, where
+            self.mul_sites.append((list(f), list(g), where))
         return self.C
 
     def sq(self, f, where, narrow=False, double=False, carried=False):
@@ -516,6 +518,32 @@ def squaring_classes():
     C, S, S2 = d["C"], d["SQ_IN"], d["SQ2_IN"]
     return {"fu_sq": (S, S), "fu_sq2": (S2, S2), "fu_sqc": (C, C), "fu_sq_x2": (S, S), "fu_sq_sq2": (S, S2),
             "fu_sq_sq2_n": (fmax_add(C, C), C), "fu_sqc_x2": (C, C)}
+
+
+def multiplication_classes():
+    """per-limb input maxima each multiplication is proven for, by function name: a pair (half 0, half 1) of lists of
+    (f maxima, g maxima, site). The single functions carry the same list twice. The wide functions take the declared
+    classes MUL_F, MUL_G, fu_mulc / fu_mulc_x2 carried x carried, and the one-MAD-wrap variants exactly the sites
+    check_group_law proves narrow, in the order Model.mul visits them (a class visited again keeps its first site's
+    name). Every class is put through prove() again here: columns below 2^64, the wrap inside the carried class, and for
+    a one-MAD wrap the top carry below 2^32. tests/probe_cases.py draws the probe's inputs from them."""
+    d = derive()
+    C, spill = d["C"], d["spill"]
+    wide = [(list(MUL_F), list(MUL_G), "declared MUL_F x MUL_G")]
+    carried = [(list(C), list(C), "carried x carried")]
+    narrow, seen = [], set()
+    for (f, g, where) in d["model"].mul_sites:
+        if (tuple(f), tuple(g)) not in seen:
+            seen.add((tuple(f), tuple(g)))
+            narrow.append((f, g, where))
+    assert narrow
+    for (f, g, where) in wide + carried + narrow:
+        _, c9, sp = prove(MCOLS, f, g, where)
+        assert sp <= spill, where
+        assert (f, g, where) in wide or c9 < 2**32, where
+    return {"fu_mul": (wide, wide), "fu_mul_x2": (wide, wide), "fu_mulc": (carried, carried),
+            "fu_mulc_x2": (carried, carried), "fu_mul_n": (narrow, narrow), "fu_mul_wn": (wide, narrow),
+            "fu_mul_nn": (narrow, narrow)}
 
 
 def derive():
